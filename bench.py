@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the MI355X proof-of-work search (BASELINE.json metric: MD5 candidates/s, GH/s).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 With --gpus N > 1 and no launcher (WORLD_SIZE unset), bench.py starts the N ranks itself
@@ -16,9 +16,15 @@ in the L = 4 chunk segment k >= 2^24), followed by the batch-boundary
 all-reduce MIN of [best index, running] over RCCL.  value = candidates hashed
 by all ranks / max-over-ranks wall time of the K timed steps.
 
-Also reported: the kernel's roofline (INT32 VALU issue, measured with HIP events
-on the search stream), time-to-secret for the BASELINE configs, and the CPU
-baseline (the oracle's restatement of the reference Go loop on the host cores).
+A plain run does only that: set up, warm up, time the K steps, write the last step's
+outputs (--dump-outputs) and print the line, with the kernel's roofline from the timed
+steps themselves (INT32 VALU issue, HIP events on the search stream).
+
+--full adds, after the line's sweep: time-to-secret for the BASELINE configs, the node's
+collective path, the secondary sweep, cancel latency, the coordinator configs, the VALU
+issue-rate probe with the committed profile's traffic and issue model, and the CPU
+baseline (the oracle's restatement of the reference Go loop on the host cores).  The
+--no-* options take single sections out of a --full run.
 """
 import argparse
 import datetime
@@ -188,9 +194,18 @@ def main(argv=None, miner_factory=None, gpu=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-probe", action="store_true", help="skip the VALU issue-rate probe")
-    ap.add_argument("--no-tts", action="store_true", help="skip the time-to-secret configs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the sweep, also run the sections beyond the headline figure: time-to-secret, "
+                         "collective, secondary sweep, cancel latency, coordinator configs, VALU probe and "
+                         "profile figures, CPU baseline (default: the sweep alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float64): the search's "
+                         "status, global_idx and secret (if any), the all-reduced [best index, running], and "
+                         "the candidates the timed steps hashed")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-probe", action="store_true", help="--full without the VALU issue-rate probe")
+    ap.add_argument("--no-tts", action="store_true",
+                    help="--full without the time-to-secret configs and the sections built on them")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="CPU baseline threads (default: every host core this process may use)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
@@ -206,6 +221,12 @@ def main(argv=None, miner_factory=None, gpu=None):
     ap.add_argument("--print-launch", action="store_true",
                     help="print the rank launcher's command (--gpus N > 1 without WORLD_SIZE) as JSON and exit")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    # the sections beyond the sweep run under --full only, less the ones a --no-* option names
+    run_tts = args.full and not args.no_tts
+    run_probe = args.full and not args.no_probe
+    run_cpu = args.full and not args.no_cpu_baseline
     gpu = gpu or TorchGPU()
     miner_factory = miner_factory or distpow.Miner
 
@@ -271,9 +292,10 @@ def main(argv=None, miner_factory=None, gpu=None):
     t_open = time.perf_counter()
     miner = miner_factory(device)
     open_ms = [(time.perf_counter() - t_open) * 1e3]
-    t_open = time.perf_counter()
-    miner_factory(device).close()
-    open_ms.append((time.perf_counter() - t_open) * 1e3)
+    if args.full:
+        t_open = time.perf_counter()
+        miner_factory(device).close()
+        open_ms.append((time.perf_counter() - t_open) * 1e3)
     dev = torch.device("cuda", device) if args.backend == "nccl" else torch.device("cpu")
     red = torch.empty(2, dtype=torch.int64, device=dev)
 
@@ -290,6 +312,7 @@ def main(argv=None, miner_factory=None, gpu=None):
             red[0] = r.global_idx if r.status == distpow.FOUND else distpow.DPOW_NO_HIT
             red[1] = 1
             dist.all_reduce(red, op=dist.ReduceOp.MIN)
+        return r
 
     def barrier():
         if dist_on:
@@ -304,7 +327,7 @@ def main(argv=None, miner_factory=None, gpu=None):
     t0 = time.perf_counter()
     timer.start()
     for s in range(args.warmup, args.warmup + args.steps):
-        step(s)
+        last = step(s)
     timer.stop()
     barrier()
     elapsed = time.perf_counter() - t0
@@ -317,6 +340,8 @@ def main(argv=None, miner_factory=None, gpu=None):
     if dist_on:
         dist.all_reduce(t, op=dist.ReduceOp.MAX, group=host_group)
     elapsed_max = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, red if dist_on else None, st)
 
     total_candidates = world * per_gpu * args.steps
     value = total_candidates / elapsed_max / 1e9
@@ -338,7 +363,7 @@ def main(argv=None, miner_factory=None, gpu=None):
                              avg_launch_ms, record_launch_ms, cand_per_launch, st, stream_ms, open_ms, cus, tpb))
 
     # time-to-secret for the BASELINE configs (deterministic answers; node-wide when world > 1)
-    if not args.no_tts:
+    if run_tts:
         guard.update("time_to_secret", section("time_to_secret", rank, time_to_secret, miner, rank, world, dev, board,
                                                barrier, gpu))
         guard.update("time_to_secret_node_search",
@@ -350,20 +375,20 @@ def main(argv=None, miner_factory=None, gpu=None):
     # The node's collective path at this world size: the batch boundary of node_mine
     # (host -> device copy, RCCL MIN all-reduce, device -> host copy, synchronize), and
     # node_mine over Miner.search for two BASELINE cases.
-    if dist_on and not args.no_tts:
+    if dist_on and run_tts:
         guard.update("collective", section("collective", rank, collective_probe, miner, rank, world, dev, board,
                                            args.backend, gpu))
 
     # Secondary sweep: the whole L = 3 chunk segment, k in [2^16, 2^24),
     # one variable message word; and the early-exit latency of a Found/Cancel (worker.go:194,209).
-    if not args.no_tts:
+    if run_tts:
         barrier()
         guard.update("secondary_sweep", section("secondary_sweep", rank, secondary_sweep, miner, wb, wbits))
         guard.update("cancel_latency_ms", section("cancel_latency", rank, cancel_latency, miner, gpu))
 
-    if rank == 0 and world == 1 and not args.no_tts:
+    if rank == 0 and world == 1 and run_tts:
         guard.update("coordinator", section("coordinator", rank, coordinator_configs))
-    if world > 1 and not args.no_tts:
+    if world > 1 and run_tts:
         # BASELINE configs 3-5 in their node shape: rank 0's process runs the coordinator mirror
         # with logical worker i on GPU i % world (coordinator.go:139-298 over W machines), while
         # the other ranks wait on a host barrier with their GPUs idle.
@@ -375,15 +400,17 @@ def main(argv=None, miner_factory=None, gpu=None):
         dist.barrier(group=host_group)
 
     probe = {}
-    if rank == 0 and not args.no_probe:
+    if rank == 0 and run_probe:
         probe = section("valu_probe", rank, valu_probe, device)
-    guard.update("valu_probe", probe)
+    if args.full:
+        guard.update("valu_probe", probe)
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and run_cpu:
         guard.update("cpu_baseline", section("cpu_baseline", rank, cpu_baseline, args.cpu_threads, args.cpu_seconds))
 
     if rank == 0:
-        guard.update("roofline", dict(guard.line["roofline"], **roofline_profile(probe, achieved_tops)))
+        if args.full:
+            guard.update("roofline", dict(guard.line["roofline"], **roofline_profile(probe, achieved_tops)))
         guard.update("ok", all(section_ok(guard.line.get(k)) for k in
                                ("time_to_secret", "collective", "secondary_sweep", "cancel_latency_ms", "coordinator",
                                 "coordinator_node", "valu_probe", "cpu_baseline")))
@@ -396,6 +423,23 @@ def main(argv=None, miner_factory=None, gpu=None):
             log(f"rank {rank}: board close: {e!r}")
     if dist_on:
         dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, result, reduced, st):
+    """--dump-outputs: what the caller of the last timed step holds, one float64 .npy per name (a
+    few numbers; indices at or above 2^53 round, DPOW_NO_HIT to 2^63).  The inputs are fixed by
+    the arguments (NONCE, SWEEP_NTZ, the step's k-window), so two builds run with the same
+    arguments compare output for output."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"status": [result.status], "global_idx": [result.global_idx],
+              "timed_candidates": [st.candidates]}
+    if result.secret is not None:
+        arrays["secret"] = list(result.secret)
+    if reduced is not None:  # [best index, running] after the step's MIN all-reduce
+        arrays["reduced"] = reduced.cpu().tolist()
+    for name, values in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(values, dtype=np.float64))
 
 
 def sweep_line(args, world, wbits, per_gpu, batch_k, value, elapsed_max, kernel_ghs, achieved_tops, avg_launch_ms,
@@ -438,7 +482,7 @@ def sweep_line(args, world, wbits, per_gpu, batch_k, value, elapsed_max, kernel_
             "launches": int(st.launches),
         },
         "stream_event_ms": round(stream_ms, 3),
-        "dpow_open_ms": {"first": round(open_ms[0], 3), "again": round(open_ms[1], 3)},
+        "dpow_open_ms": dict(zip(("first", "again"), (round(ms, 3) for ms in open_ms))),
         "geometry": {"cus": cus, "threads_per_block": tpb},
         "build_id": distpow.build_id(),  # = the sources' hash (distpow._lib.check_build refused anything else)
     }

@@ -17,7 +17,7 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FAKES = os.path.join(ROOT, "tests", "_bench_fakes.py")
-BENCH_ARGS = ["--steps", "2", "--warmup", "1", "--no-probe", "--no-cpu-baseline", "--backend", "gloo"]
+BENCH_ARGS = ["--full", "--steps", "2", "--warmup", "1", "--no-probe", "--no-cpu-baseline", "--backend", "gloo"]
 
 
 def _port():
@@ -124,6 +124,33 @@ def test_stdout_carries_only_the_json_line():
     assert r.returncode == 0, r.stderr
     assert r.stdout.splitlines() == ['{"metric": "m", "value": 1}'], r.stdout
     assert "RCCL version" in r.stderr and "a python print" in r.stderr
+
+
+def test_plain_run_is_the_sweep_alone_and_dumps_its_outputs(tmp_path):
+    """Without --full the line holds the sweep and none of the later sections; --dump-outputs
+    writes what the last timed step returned, the same from run to run."""
+    import numpy as np
+    plain = ["--steps", "3", "--warmup", "1", "--backend", "gloo"]
+    dumps = []
+    for d in ("a", "b"):
+        outs, _ = _ranks(1, [], plain + ["--dump-outputs", str(tmp_path / d)])
+        rc, out, err = outs[0]
+        assert rc == 0, err[-3000:]
+        rec = _line(out)
+        assert rec["ok"] is True and rec["value"] > 0 and rec["steps"] == 3 and rec["ms_per_step"] > 0
+        assert rec["roofline"]["launches"] == 3  # --steps sets the timed steps
+        for k in ("time_to_secret", "collective", "secondary_sweep", "cancel_latency_ms", "coordinator",
+                  "valu_probe", "cpu_baseline"):
+            assert k not in rec, k
+        files = sorted(p.name for p in (tmp_path / d).iterdir())
+        assert files == ["global_idx.npy", "reduced.npy", "status.npy", "timed_candidates.npy"]
+        dumps.append({f: np.load(tmp_path / d / f) for f in files})
+    a, b = dumps
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert all(np.array_equal(a[f], b[f]) for f in a)
+    assert a["status.npy"].tolist() == [0] and a["global_idx.npy"].tolist() == [float(1 << 63)]  # EXHAUSTED, no hit
+    assert a["reduced.npy"].tolist() == [float(1 << 63), 1.0]  # MIN of [DPOW_NO_HIT, running]
+    assert a["timed_candidates.npy"].tolist() == [3.0 * (1 << 36)]
 
 
 def test_collective_reports_both_boundaries():

@@ -44,8 +44,8 @@ tests() {
 check() {
     mkdir -p $out/tts
     tests &&
-    timeout -k 10 300 python3 bench.py > $out/bench.json 2> $out/bench.err &&
-    timeout -k 10 300 python3 bench.py --gpus 2 --backend gloo --same-device --steps 2 --warmup 1 --no-probe \
+    timeout -k 10 300 python3 bench.py --full > $out/bench.json 2> $out/bench.err &&
+    timeout -k 10 300 python3 bench.py --full --gpus 2 --backend gloo --same-device --steps 2 --warmup 1 --no-probe \
         --no-cpu-baseline > $out/bench_n2.json 2> $out/bench_n2.err &&
     timeout -k 10 120 rocprofv3 --kernel-trace --output-format csv -d $out/tts/trace -o run -- \
         python3 tools/tts_trace.py > $out/tts/tts.json 2> $out/tts/tts.err
@@ -54,7 +54,7 @@ check() {
 rehearse() {
     local n=${1:-8}
     timeout -k 10 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 \
-        --master-port 29513 bench.py --gpus $n --steps 2 --warmup 1 --backend gloo --same-device --no-probe \
+        --master-port 29513 bench.py --full --gpus $n --steps 2 --warmup 1 --backend gloo --same-device --no-probe \
         > $out/bench_n$n.json 2> $out/bench_n$n.err
 }
 
@@ -66,7 +66,7 @@ final)
     timeout -k 10 400 python3 -u tools/node_probe.py 3 > $out/node_probe.json 2> $out/node_probe.err &&
     timeout -k 10 300 python3 -u tests/soak/layout_check.py > $out/layout_check.json 2> $out/layout_check.err &&
     timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1 &&
-    timeout -k 10 600 python3 bench.py --gpus 8 --backend gloo --same-device --steps 2 --warmup 1 --no-probe \
+    timeout -k 10 600 python3 bench.py --full --gpus 8 --backend gloo --same-device --steps 2 --warmup 1 --no-probe \
         > $out/bench_n8.json 2> $out/bench_n8.err &&
     bash tools/profile_gpu.sh $tag pmc > $out/profile.list 2>&1 ;;
 node) timeout -k 10 600 python3 -u tools/node_probe.py "${1:-3}" "${2:-2,4,8}" $3 > $out/node_probe.json 2> $out/node_probe.err ;;

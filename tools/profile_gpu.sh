@@ -7,7 +7,7 @@ TAG=${1:?tag}
 OUT=gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-BENCH="bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-probe"
+BENCH="bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-probe"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run -- \
     python3 $BENCH > "$OUT/bench.json" 2> "$OUT/trace.err"
 if [ "${2:-}" = "pmc" ]; then

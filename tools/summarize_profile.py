@@ -44,7 +44,7 @@ def main():
     big = int(sweep[bench["warmup"] * per_step]["Grid_Size_X"])
     summary = {
         "kernel": sweep[0]["Kernel_Name"],
-        "bench_command": "python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-probe",
+        "bench_command": "python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-probe",
         "timed_sweep_launches": len(timed),
         "timed_sweep_avg_launch_ms": sum(timed) / len(timed),
         "bench_avg_launch_ms_hip_events": bench["roofline"]["avg_launch_ms"],
