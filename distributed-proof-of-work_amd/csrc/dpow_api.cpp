@@ -629,8 +629,10 @@ int search_window(dpow_ctx *c, const uint8_t *nonce, size_t nonce_len, uint32_t 
         }
         const uint64_t share = grid_share(active, c->knobs);
         cap_shared_launch(planner, pl, active, c->knobs);
+        const bool seg_inner = seg_inner_select(planner, pl, ntz, c->knobs.seg_inner);
         uint64_t worker_blocks = 0;
         rc = size_search_launch(pl, ntz, c->cus, share, c->knobs, &worker_blocks, active);
+        if (rc >= 0 && seg_inner) rc = seg_inner_size(pl, worker_blocks, &worker_blocks);
         if (rc < 0) return set_error(rc, "dpow_search: launch grid leaves a claim counter without waves");
         done_target += (uint32_t)worker_blocks;  // retirement is counted per workgroup
         L.claim = c->d_claims + (li % kClaimRing) * kClaimSlot;
@@ -650,7 +652,7 @@ int search_window(dpow_ctx *c, const uint8_t *nonce, size_t nonce_len, uint32_t 
                           c->stream);
         if (e != hipSuccess) return hip_fail(e, "search_launch");
         if (!md5_queued) c->diag_t[1] = now_ns() - sw.t0;
-        diag_queued(li, seq, 1, L.i_end - L.i_begin, pl.info.k_end << 8);
+        diag_queued(li, seq, L.n_seg != 0u ? 2 : 1, L.i_end - L.i_begin, pl.info.k_end << 8);
         md5_queued = true;
         slot.seq = seq;
         slot.in_flight = true;
@@ -816,6 +818,8 @@ int dpow_open(int device, dpow_ctx **out) {
     if (const char *pw = getenv("DPOW_DIAG_CPW")) c->knobs.cpw = (uint32_t)std::max(0, atoi(pw));
     if (const char *pw = getenv("DPOW_DIAG_SHARE_LAUNCH_US")) c->knobs.share_launch_us = (uint32_t)std::max(0, atoi(pw));
     if (const char *pw = getenv("DPOW_DIAG_SHARE_MAX")) c->knobs.share_max = (uint32_t)std::max(0, atoi(pw));
+    // DPOW_DIAG_SEG_INNER: 0 = no segment-inner launch, 1 = wherever the shape permits (plan.h)
+    if (const char *pw = getenv("DPOW_DIAG_SEG_INNER")) c->knobs.seg_inner = atoi(pw) != 0 ? 1 : 0;
     if (const char *pw = getenv("DPOW_DIAG_MIN_CHUNK")) {
         const uint32_t v = (uint32_t)std::max(0, atoi(pw));
         if (v && !(v & (v - 1))) c->knobs.min_chunk = v;
@@ -1393,13 +1397,17 @@ int dpow_plan_candidate(const uint8_t *nonce, size_t nonce_len, uint32_t worker_
     return 0;
 }
 
-int dpow_diag_launch_geometry(const uint8_t *nonce, size_t nonce_len, uint32_t ntz, uint32_t worker_byte,
-                              uint32_t worker_bits, uint64_t k_begin, uint64_t k_end, uint32_t cus, uint32_t share,
-                              dpow_diag_launch *out, size_t max_launches) {
-    if (cus == 0 || share == 0) return set_error(DPOW_EINVAL, "dpow_diag_launch_geometry: cus and share must be > 0");
+namespace {
+// The launches of a window as dpow_search sizes them.  recut: a segment-inner launch's claims as
+// its kernel gets them (seg_inner_size); without it they stay as size_search_launch cut them, in
+// index order, and only n_seg says that the search re-cuts them.
+int launch_geometry(const char *who, const uint8_t *nonce, size_t nonce_len, uint32_t ntz, uint32_t worker_byte,
+                    uint32_t worker_bits, uint64_t k_begin, uint64_t k_end, uint32_t cus, uint32_t share,
+                    int seg_inner_mode, bool recut, dpow_diag_launch *out, size_t max_launches) {
+    if (cus == 0 || share == 0) return set_error(DPOW_EINVAL, who);
     WindowPlanner planner;
     const int rc = planner.init(nonce, nonce_len, ntz, worker_byte, worker_bits, k_begin, k_end);
-    if (rc < 0) return set_error(rc, "dpow_diag_launch_geometry: bad arguments");
+    if (rc < 0) return set_error(rc, who);
     PlannedLaunch pl;
     size_t n = 0;
     const LaunchKnobs policy{};
@@ -1407,9 +1415,21 @@ int dpow_diag_launch_geometry(const uint8_t *nonce, size_t nonce_len, uint32_t n
         if (pl.k0) continue;  // k = 0: the search's k = 0 kernel, not an md5 launch
         // share = searches in flight on the device, as dpow_search sees them (g_active)
         cap_shared_launch(planner, pl, share, policy);
+        const bool seg_inner = seg_inner_select(planner, pl, ntz, seg_inner_mode);
         uint64_t wblocks = 0;
-        const int r = size_search_launch(pl, ntz, cus, grid_share(share, policy), policy, &wblocks, share);
-        if (r < 0) return set_error(r, "dpow_diag_launch_geometry: launch grid leaves a claim counter without waves");
+        int r = size_search_launch(pl, ntz, cus, grid_share(share, policy), policy, &wblocks, share);
+        uint32_t n_seg = 0;
+        if (r >= 0 && seg_inner) {
+            PlannedLaunch cut = pl;
+            uint64_t wb2 = wblocks;
+            r = seg_inner_size(cut, wblocks, &wb2);
+            n_seg = cut.L.n_seg;
+            if (recut) {
+                pl = cut;
+                wblocks = wb2;
+            }
+        }
+        if (r < 0) return set_error(r, who);
         if (out && n < max_launches) {
             dpow_diag_launch &d = out[n];
             d.k_begin = pl.info.k_begin;
@@ -1427,10 +1447,54 @@ int dpow_diag_launch_geometry(const uint8_t *nonce, size_t nonce_len, uint32_t n
             d.wave_block = kWaveBlock;
             d.n_static = pl.L.n_static;
             d.poll_wb = pl.L.poll_wb;
+            d.n_seg = n_seg;
         }
         ++n;
     }
     return (int)n;
+}
+}  // namespace
+
+int dpow_diag_launch_geometry(const uint8_t *nonce, size_t nonce_len, uint32_t ntz, uint32_t worker_byte,
+                              uint32_t worker_bits, uint64_t k_begin, uint64_t k_end, uint32_t cus, uint32_t share,
+                              dpow_diag_launch *out, size_t max_launches) {
+    return launch_geometry("dpow_diag_launch_geometry: bad arguments or grid", nonce, nonce_len, ntz, worker_byte,
+                           worker_bits, k_begin, k_end, cus, share, -1, false, out, max_launches);
+}
+
+int dpow_diag_seg_inner_geometry(const uint8_t *nonce, size_t nonce_len, uint32_t ntz, uint32_t worker_byte,
+                                 uint32_t worker_bits, uint64_t k_begin, uint64_t k_end, uint32_t cus, int mode,
+                                 dpow_diag_launch *out, size_t max_launches) {
+    return launch_geometry("dpow_diag_seg_inner_geometry: bad arguments or grid", nonce, nonce_len, ntz,
+                           worker_byte, worker_bits, k_begin, k_end, cus, 1, mode, true, out, max_launches);
+}
+
+int dpow_diag_seg_inner_candidate(const uint8_t *nonce, size_t nonce_len, uint32_t ntz, uint32_t worker_byte,
+                                  uint32_t worker_bits, uint64_t k_begin, uint64_t k_end, int mode,
+                                  uint64_t local_idx, uint32_t iv_out[4], uint32_t words_out[32],
+                                  uint32_t *nblk_out) {
+    if (!iv_out || !words_out || !nblk_out)
+        return set_error(DPOW_EINVAL, "dpow_diag_seg_inner_candidate: NULL argument");
+    WindowPlanner planner;
+    const int rc = planner.init(nonce, nonce_len, ntz, worker_byte, worker_bits, k_begin, k_end);
+    if (rc < 0) return set_error(rc, "dpow_diag_seg_inner_candidate: bad arguments");
+    PlannedLaunch pl;
+    const LaunchKnobs policy{};
+    while (planner.next(pl)) {
+        if (pl.k0) continue;
+        const bool seg_inner = seg_inner_select(planner, pl, ntz, mode);
+        if (local_idx < pl.L.i_begin || local_idx >= pl.L.i_end) continue;
+        uint64_t wblocks = 0;
+        int r = size_search_launch(pl, ntz, 256, 1, policy, &wblocks, 1);
+        if (r >= 0 && seg_inner) r = seg_inner_size(pl, wblocks, &wblocks);
+        if (r < 0) return set_error(r, "dpow_diag_seg_inner_candidate: sizing failed");
+        for (int w = 0; w < 4; ++w) iv_out[w] = pl.L.iv[w];
+        memset(words_out, 0, 32 * sizeof(uint32_t));
+        candidate_words(pl, local_idx, words_out);
+        *nblk_out = pl.info.nblk;
+        return seg_inner ? 1 : 0;
+    }
+    return set_error(DPOW_EINVAL, "dpow_diag_seg_inner_candidate: index outside the window");
 }
 
 int dpow_diag_node_alias(dpow_ctx *c, void **cached, void **lookup) {

@@ -132,8 +132,9 @@ struct Launch {
     uint64_t n_static;     // claims [0, n_static) are handed out by wave index, not by a counter: worker
                            //  wave w's first claim is w (the "_ls" kernels only; 0 for every other launch)
     uint32_t poll_wb;      // wave-blocks per group: a wave reads Ctrl::best / Ctrl::stop once per group
-    uint32_t reserved0;    // (round 4's fair-priority tick count; kept so the kernel argument layout,
-                           //  and with it the kernels' code, stays as measured)
+    uint32_t n_seg;        // segment-inner launches (md5_search_kernel.h search_body_si): the 2^24-k segments
+                           //  the window lies in; wb_begin / n_wblocks / the claims then describe ONE
+                           //  segment's index range.  0: every other launch (index order)
     unsigned long long *claim;  // this launch's kClaimCounters counters (zero at launch start;
                                 //  the launch's last workgroup re-zeroes them for the slot's next user)
     Ctrl *ctrl;              // this search's control block (clean at its first launch)
@@ -209,6 +210,10 @@ DPOW_HD uint32_t tail_prefilter_le(uint32_t n) {
     const uint32_t e = (n < 8 ? n : 8) & ~1u;  // even part
     return e == 0 ? 0xFFFFFFFFu : e >= 8 ? 0u : (0xFFFFFFFFu >> (4 * e));
 }
+
+// Layouts with a segment-inner kernel (md5_search_kernel.h search_body_si; md5_variant.hip's "_si"
+// unit): one final block, SH = 0, W0 <= 3 (nonces of 0, 4, 8 and 12 bytes).
+DPOW_HD bool seg_inner_layout(uint32_t nblk, uint32_t w0, uint32_t sh) { return nblk == 1 && sh == 0 && w0 <= 3; }
 
 // Kernels with the D-equality test: one final block (D = iv[3] + state word)
 // and a test on the whole D word.

@@ -5,6 +5,11 @@ namespace dpow {
 
 hipError_t search_launch(int nblk, int w0, int sh, const Launch &L, uint32_t grid, hipStream_t stream) {
     if (!variant_exists(nblk, w0, sh)) return hipErrorInvalidValue;
+    if (L.n_seg != 0u) {  // segment-inner order: its own kernels, and no other reads the claims that way
+        if (!seg_inner_exists(nblk, w0, sh) || !use_d_equality((uint32_t)nblk, L.ntz) || L.seg0 == kLsegBase)
+            return hipErrorInvalidValue;
+        return variant_launch_1_0_si(w0, L, grid, stream);
+    }
     if (L.seg0 == kLsegBase) {
         if (sh != 0) return hipErrorInvalidValue;
         return nblk == 1 ? variant_launch_1_0_ls(w0, L, grid, stream)
@@ -34,7 +39,7 @@ hipError_t search_prepare() {
     if (e == hipSuccess) e = variant_prepare_##n##_##s();
     DPOW_PREP(1, 0) DPOW_PREP(1, 1) DPOW_PREP(1, 2) DPOW_PREP(1, 3)
     DPOW_PREP(2, 0) DPOW_PREP(2, 1) DPOW_PREP(2, 2) DPOW_PREP(2, 3)
-    DPOW_PREP(1, 0_ls) DPOW_PREP(2, 0_ls)
+    DPOW_PREP(1, 0_ls) DPOW_PREP(2, 0_ls) DPOW_PREP(1, 0_si)
 #undef DPOW_PREP
     return e;
 }

@@ -41,8 +41,41 @@
 #ifndef DPOW_VLS
 #define DPOW_VLS 0
 #endif
+// DPOW_VSI = 1 (md5_variant.hip's "_si" translation unit): the segment-inner kernels of the
+// one-block SH = 0 D-equality layouts (search_body_si below): a wave keeps its wave-block and
+// walks the launch's 2^24-k segments as its inner loop, so everything that depends on word W0
+// alone is computed once per wave-block and reused for every segment.  Their own unit and
+// namespace: the other units' kernels keep their code.
+#ifndef DPOW_VSI
+#define DPOW_VSI 0
+#endif
+// Build choices of the segment-inner unit (A/B builds: Makefile SIFLAGS): the pipe start, s_nop in
+// front of the worker path (code placement) and whether the segment word's K + M constants live
+// in VGPRs (a v_mov each per iteration) or SGPRs.  Same-box sweep of one start for every covered
+// W0 (profiles/seg_inner_lead_sweep.json; GH/s on the 16-segment bench step, index order first):
+//   W0   index  lead 2     3     4     5     6     7   5 + VGPR constants
+//    0   217.0   224.4 224.9 200.1 225.7 215.2 221.1   224.4
+//    1   217.8   226.8 207.0 200.2 226.2 226.6 224.8   229.1
+//    2   224.6   208.2 229.5 207.2 232.9 231.5 228.4   233.2
+//    3   227.8   232.7 212.0 207.2 236.6 235.9 233.8   236.7
+// The index-ordered kernels' starts (pipe_lead: 2, 4, 3, 3) do not carry over: 4 is the worst
+// start of every layout here (-8 to -9 % against index order), 5 the best of every one.
+#ifndef DPOW_SI_LEAD
+#define DPOW_SI_LEAD 5
+#endif
+#ifndef DPOW_SI_PAD
+#define DPOW_SI_PAD 0
+#endif
+#ifndef DPOW_SI_VSEG
+#define DPOW_SI_VSEG 1
+#endif
+#if DPOW_VLS && DPOW_VSI
+#error "DPOW_VLS and DPOW_VSI are separate units"
+#endif
 #if DPOW_VLS
 #define DPOW_KNS lsk
+#elif DPOW_VSI
+#define DPOW_KNS sik
 #else
 #define DPOW_KNS k
 #endif
@@ -247,18 +280,21 @@ struct VgprK {
     // First step of block 0 in the hand-ordered pipeline (md5_tail's kI0 for
     // the hash loop's ONLY_D call with kNC candidates).
     static constexpr int kEnd0 = NBLK == 1 ? 62 : 64;
-    static constexpr int kLead = pipe_lead(NBLK, W0, SH, kNarrow);
+    static constexpr int kLead = DPOW_VSI && DPOW_SI_LEAD > 0 ? DPOW_SI_LEAD : pipe_lead(NBLK, W0, SH, kNarrow);
     static constexpr int kI0 = W0 + kLead < kEnd0 ? W0 + kLead : kEnd0;
     // Steps the hash loop runs (ONLY_D: the last block stops after step 61).
     static constexpr bool run(int blk, int i) { return !(blk == NBLK - 1 && i >= 62); }
     // Steps reading a segment word: always held in VGPRs (updated at segment changes).
-    static constexpr bool seg(int blk, int i) { return seg_word<NBLK, W0, SH>(16 * blk + md5_word(i)) && run(blk, i); }
+    // (the segment-inner unit rewrites them every iteration of its segment loop; built with
+    // DPOW_SI_VSEG = 0 it takes them from SGPRs instead: StepWord::km's seg_add path)
+    static constexpr bool segw(int blk, int i) { return seg_word<NBLK, W0, SH>(16 * blk + md5_word(i)) && run(blk, i); }
+    static constexpr bool seg(int blk, int i) { return (!DPOW_VSI || DPOW_SI_VSEG) && segw(blk, i); }
     static constexpr bool eligible(int blk, int i) {
         const int m = 16 * blk + md5_word(i);
         const bool zero = m > W0 + 2 && m != 16 * NBLK - 2;
         const bool lane = m == W0 || (SH != 0 && m == W0 + 1);
         const bool piped = blk > 0 || i >= kI0;
-        return !zero && !lane && piped && run(blk, i) && !seg(blk, i);
+        return !zero && !lane && piped && run(blk, i) && !segw(blk, i);
     }
     static constexpr int rank(int blk, int i) {
         int r = 0;
@@ -373,7 +409,18 @@ struct VarWords {
     uint32_t seg_d[3];   // segment-word additions (seg_add) for the steps that read them from L.KT
                          //  (full_check's steps 62-63 of the last block only; the hash loop holds them
                          //  all in kc)
+#if DPOW_VSI
+    uint32_t w0km[4][kNC];  // K + M of round r's step reading word W0 (per lane; loop-invariant in the
+                            //  segment loop, where seg_d[0] is the current segment's addition to word W0 + 1)
+#endif
 };
+
+// Step of round r (block-relative) that reads message word w.
+constexpr int step_of_word(int r, int w) {
+    for (int i = 16 * r; i < 16 * r + 16; ++i)
+        if (md5_word(i) == w) return i;
+    return -1;
+}
 
 // K + M of step I of block BLK for candidate j (the message word M includes the
 // candidate's variable bytes when the step reads word W0, or W0 + 1 for SH != 0).
@@ -390,7 +437,11 @@ struct StepWord {
     static DPOW_DEV uint32_t km(const Launch &L, const VarWords<KS> &v, int j) {
         uint32_t k = zero_word ? kMd5K[I] : vgpr_k ? v.kc->v[64 * BLK + I] : L.KT[64 * BLK + I];
         if constexpr (seg && !vgpr_k) k += seg_add<NBLK, W0>(m, v.seg_d);
+#if DPOW_VSI
+        if constexpr (m == W0) k = v.w0km[I / 16][j];
+#else
         if constexpr (m == W0) k = (k + v.lo_s[j]) + v.lo_v;
+#endif
         if constexpr (SH != 0 && m == W0 + 1) {
             k += v.hi_s[j];                        // SALU: K + M stays uniform
             if constexpr (SH == 3 && KS) k += v.lane_k;  // the one VALU add of the step
@@ -625,6 +676,19 @@ DPOW_DEV void var_words(V &v, int j, uint32_t vs, uint32_t loff, uint32_t d1) {
     }
 }
 
+#if DPOW_VSI
+// The four K + M values of word W0 for slot j (one final block), from lo_s / lo_v.
+template <int W0, class V>
+DPOW_DEV void w0km_fill(V &v, int j, const Launch &L) {
+    constexpr int i0 = step_of_word(0, W0), i1 = step_of_word(1, W0), i2 = step_of_word(2, W0),
+                  i3 = step_of_word(3, W0);
+    v.w0km[0][j] = (L.KT[i0] + v.lo_s[j]) + v.lo_v;
+    v.w0km[1][j] = (L.KT[i1] + v.lo_s[j]) + v.lo_v;
+    v.w0km[2][j] = (L.KT[i2] + v.lo_s[j]) + v.lo_v;
+    v.w0km[3][j] = (L.KT[i3] + v.lo_s[j]) + v.lo_v;
+}
+#endif
+
 // Full digest test of one lane's candidate (rare path: only when the D-word
 // test passed and ntz > 8, i.e. probability 2^-32 per candidate).
 // loff: the lane offset, plus (SH = 0) the segment's addition to word W0 (search_body lov);
@@ -640,6 +704,9 @@ DPOW_DEV bool full_check(const Launch &L, const KConst &kc, uint32_t vs, uint32_
     v.seg_d[1] = sd[1];
     v.seg_d[2] = sd[2];
     var_words<SH>(v, 0, vs, loff, v.seg_d[0]);
+#if DPOW_VSI
+    w0km_fill<W0>(v, 0, L);
+#endif
     uint32_t out[4][kNC];
     md5_tail<NBLK, W0, SH, 1>(out, L, v);
     return trailing_zero_nibbles(out[0][0], out[1][0], out[2][0], out[3][0]) >= L.ntz;
@@ -1225,22 +1292,276 @@ DPOW_DEV void search_body(const Launch &L) {
     }
 }
 
+#if DPOW_VSI
+// ---------------------------------------------------------------------------
+// Segment-inner order (Launch::n_seg != 0; one final block, SH = 0, the D-equality test).
+//
+// The launch's window lies in n_seg consecutive 2^24-k segments from segment seg_first.
+// Its wave-blocks are those of ONE segment's local-index range: wave-block b is the 64 * kNC
+// indices from offset o = b * 64 * kNC of a segment (wb_begin = the first segment's first
+// index, n_wblocks = a segment's wave-blocks), and the wave that claims it hashes it in every
+// segment s whose copy wb_begin + (s << (24 + rbits)) + o intersects [i_begin, i_end), s
+// increasing.  Word W0 (threadByte | k_lo24 << 8) depends on o and the lane only, word W0 + 1
+// (k >> 24) on s only, so per wave-block and slot the wave computes once
+//   - step W0 whole (its inputs: the uniform state of steps 0 .. W0 - 1 and the lane's W0),
+//   - a + F(b, c, d) of step W0 + 1 (F's inputs are the step-W0 word and uniform words),
+//   - K + M[W0] of the three later steps that read word W0,
+// and each segment's hash starts at step W0 + 1 with add(P, K + M[W0 + 1]), rotate, add.
+//
+// Exactness: the answer is still the atomicMin over global indices.  (o, s) -> index is
+// increasing in s, so a wave-block leaves its segment loop at the first s whose first index
+// is at or above the best seen, or on a hit of its own; a claim whose first wave-block has no
+// segment below the best ends the wave (every later wave-block lies higher in every segment).
+// Every candidate below the returned index is hashed.
+constexpr uint32_t kSegLimitNone = 0xFFFFFFFFu;
+
+// Smallest local index whose global index is >= g (global_of_local is increasing).
+DPOW_DEV uint64_t local_ceil_of_global(uint64_t g, uint32_t rbits, uint32_t base_tb) {
+    const uint64_t k = g >> 8;
+    const uint32_t tb = (uint32_t)(g & 0xFFu);
+    if (tb < base_tb) return k << rbits;
+    const uint32_t t = tb - base_tb;
+    return t >> rbits ? (k + 1u) << rbits : (k << rbits) + t;
+}
+
+// The segments of a wave-block at segment offset o that lie below the best index: s < q, and
+// s == q when o < r, for (q, r) = the best's local index relative to wb_begin, split at a
+// segment's size.
+struct SegLimit {
+    uint32_t q, r;
+};
+DPOW_DEV SegLimit seg_limit_of(const Launch &L, unsigned long long best) {
+    const uint32_t segbits = 24u + L.rbits;
+    const uint64_t ib = local_ceil_of_global(best, L.rbits, L.base_tb);
+    const uint64_t rel = ib > L.wb_begin ? ib - L.wb_begin : 0ull;
+    const uint64_t q = rel >> segbits;
+    SegLimit l;
+    l.q = q >= (uint64_t)kSegLimitNone ? kSegLimitNone - 1u : (uint32_t)q;
+    l.r = (uint32_t)(rel - (q << segbits));
+    return l;
+}
+DPOW_DEV uint32_t seg_limit_at(const SegLimit &l, uint32_t o) { return l.q + (o < l.r ? 1u : 0u); }
+
+// The lane invariants of one wave-block: the state after step W0 and step W0 + 1's a + F.
+template <int NBLK, int W0, int SH>
+DPOW_DEV void seg_invariants(uint32_t (&x)[4][kNC], uint32_t (&p)[kNC], const Launch &L, VarWords<true> &v) {
+#pragma unroll
+    for (int j = 0; j < kNC; ++j) {
+        x[0][j] = L.iv[0]; x[1][j] = L.iv[1]; x[2][j] = L.iv[2]; x[3][j] = L.iv[3];
+    }
+    md5_steps<NBLK, W0, SH, 0, 0, W0 + 1, kNC>(x, L, v);
+    constexpr int I = W0 + 1;
+    constexpr int ai = (64 - I) % 4, bi = (ai + 1) % 4, ci = (ai + 2) % 4, di = (ai + 3) % 4;
+#pragma unroll
+    for (int j = 0; j < kNC; ++j) {
+        p[j] = x[ai][j] + md5_fn<I>(x[bi][j], x[ci][j], x[di][j]);
+        // held in VGPRs across the segment loop, not recomputed in it
+        asm volatile("" : "+v"(p[j]), "+v"(x[(64 - W0) % 4][j]));
+        asm volatile("" : "+v"(v.w0km[1][j]), "+v"(v.w0km[2][j]), "+v"(v.w0km[3][j]));
+    }
+}
+
+// One wave-block of segment s (v.seg_d[0] = s: the addition to word W0 + 1): steps W0 + 1 .. 61
+// from the invariants, the D-equality test and the hit path of hash_wave_block.
+template <int NBLK, int W0, int SH>
+DPOW_DEV uint64_t hash_wave_block_si(const Launch &L, const KConst &kc, const uint32_t (&xin)[4][kNC],
+                                     const uint32_t (&p)[kNC], const VarWords<true> &v, const uint32_t (&vs)[kNC],
+                                     uint32_t s, uint32_t o, uint32_t lane, uint32_t loff) {
+    constexpr int kLead = VgprK<NBLK, W0, SH, true>::kLead;
+    constexpr int kI0 = W0 + kLead < 62 ? W0 + kLead : 62;
+    static_assert(kLead >= 2, "steps W0 and W0 + 1 precede the hand-ordered pipeline");
+    uint32_t x[4][kNC];
+#pragma unroll
+    for (int j = 0; j < kNC; ++j)
+#pragma unroll
+        for (int w = 0; w < 4; ++w) x[w][j] = xin[w][j];
+    {
+        constexpr int I = W0 + 1;
+        constexpr int ai = (64 - I) % 4, bi = (ai + 1) % 4;
+        const uint32_t km = L.KT[I] + v.seg_d[0];
+#pragma unroll
+        for (int j = 0; j < kNC; ++j) x[ai][j] = x[bi][j] + __builtin_rotateleft32(p[j] + km, md5_shift(I));
+    }
+    md5_steps<NBLK, W0, SH, 0, W0 + 2, kI0, kNC>(x, L, v);
+    pipe::steps<NBLK, W0, SH, 0, kI0, 62>(x, L, v);
+
+    uint64_t bal[kNC];
+    uint64_t any = 0;
+#pragma unroll
+    for (int j = 0; j < kNC; ++j) {
+        bal[j] = __ballot(x[3][j] == L.deq);
+        any |= bal[j];
+    }
+    if (any != 0) {  // rare: lowest valid slot, then lowest lane
+        const uint64_t i0 = L.wb_begin + ((uint64_t)s << (24u + L.rbits)) + o;
+#pragma unroll
+        for (int j = 0; j < kNC; ++j) {
+            const uint64_t ij = i0 + 64u * j;
+            uint64_t m = bal[j] & lane_range_mask((int64_t)(L.i_begin - ij), (int64_t)(L.i_end - ij));
+            if (m != 0 && L.ntz > 8u) {
+                const uint32_t sd[3] = {v.seg_d[0], 0u, 0u};
+                const bool ok = ((m >> lane) & 1ull) && full_check<NBLK, W0, SH, true>(L, kc, vs[j], loff, sd);
+                m = __ballot(ok);
+            }
+            if (m != 0) {
+                const uint64_t g = global_of_local(ij + (uint64_t)__builtin_ctzll(m), L.rbits, L.base_tb);
+                if (lane == 0) {
+                    // (a returning atomic whose result is consumed: hash_wave_block)
+                    const unsigned long long prev = __hip_atomic_fetch_min(
+                        &L.ctrl->best, (unsigned long long)g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    asm volatile("; dpow: atomicMin performed (%0)" ::"v"(prev));
+                }
+                return g;
+            }
+        }
+    }
+    return kNoHitG;
+}
+
+template <int NBLK, int W0, int SH, bool EQ>
+DPOW_DEV void search_body_si(const Launch &L) {
+    static_assert(NBLK == 1 && SH == 0 && EQ && W0 + 1 != 16 * NBLK - 2,
+                  "segment-inner: one final block, SH = 0, D-equality, W0 + 1 not the bit-length word");
+    if (blockIdx.x == 0) {  // dispatched first: the watcher
+        watcher(L);
+        return;
+    }
+#if DPOW_SI_PAD
+    asm volatile(".rept %0\n s_nop 0\n .endr" ::"i"(DPOW_SI_PAD));
+#endif
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t loff = lane_offset(L.rbits, lane);
+    KConst kc;
+    kconst_init<NBLK, W0, SH, 0, 0, true>(kc, L);
+
+    unsigned long long best = __hip_atomic_load(&L.ctrl->best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    best = best < L.bound0 ? best : L.bound0;
+    uint32_t stop = __hip_atomic_load(&L.ctrl->stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+
+    // Claims, claim-ahead, guided tail, tail priority and retirement as in search_body; a
+    // claim's wave-blocks are wave-blocks of a segment's range, each hashed in every segment.
+    __builtin_amdgcn_s_setprio(1);
+    uint32_t x = (blockIdx.x - 1u) % kClaimCounters;
+    const bool skip = stop != 0u || global_of_local(L.i_begin, L.rbits, L.base_tb) >= best;
+    uint64_t claim = skip ? L.n_chunks : claim_next(L.claim + x * kClaimStride, x, lane, 0);
+    const uint32_t segbits = 24u + L.rbits;
+    SegLimit lim = seg_limit_of(L, best);
+    // Ctrl::best / Ctrl::stop once per poll_wb hashed wave-blocks, whichever wave-block or
+    // claim they belong to: the loads are issued at one poll and consumed at the next.
+    uint32_t pc = L.poll_wb;
+    unsigned long long best_seen = __hip_atomic_load(&L.ctrl->best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    uint32_t stop_seen = __hip_atomic_load(&L.ctrl->stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    uint32_t hops = 0;
+    for (;;) {
+        if (claim >= L.n_chunks) {  // this counter is drained: the next one (search_body)
+            if (skip || ++hops >= kClaimCounters) break;
+            x = (x + 1u) % kClaimCounters;
+            const unsigned long long seen =
+                __hip_atomic_load(L.claim + x * kClaimStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            claim = seen * kClaimCounters + x < L.n_chunks ? claim_next(L.claim + x * kClaimStride, x, lane, 0)
+                                                           : L.n_chunks;
+            continue;
+        }
+        unsigned long long next_v = 0;
+        bool issued = false;
+        const bool big = claim < L.n_big;
+        if (!big) __builtin_amdgcn_s_setprio(0);
+        const uint64_t b_begin = big ? claim * L.chunk : L.n_big * L.chunk + (claim - L.n_big) * L.chunk_tail;
+        const uint32_t csz = big ? L.chunk : L.chunk_tail;
+        const uint32_t nb = (uint32_t)(b_begin + csz < L.n_wblocks ? csz : L.n_wblocks - b_begin);
+        uint32_t o = (uint32_t)(b_begin * (uint64_t)kWaveBlock);  // < 2^(24 + rbits) <= 2^32
+        bool over = false;  // nothing below the best is left from this wave-block on
+        for (uint32_t left = nb; left != 0 && stop == 0u; --left, o += (uint32_t)kWaveBlock) {
+            // the segments [s, s_hi) in which this wave-block intersects the window
+            uint32_t s = L.wb_begin + o + (uint64_t)kWaveBlock <= L.i_begin ? 1u : 0u;
+            const uint32_t s_hi =
+                L.n_seg - (L.wb_begin + ((uint64_t)(L.n_seg - 1u) << segbits) + o >= L.i_end ? 1u : 0u);
+            uint32_t s_end = seg_limit_at(lim, o);
+            if (s_end == 0u) {  // the best lies in the first segment at or below o: so does it for every later o
+                over = true;
+                break;
+            }
+            s_end = s_end < s_hi ? s_end : s_hi;
+            if (left == 1u) {  // the claim's last wave-block: reserve the next claim now
+                next_v = claim_issue<true>(L.claim + x * kClaimStride, lane);
+                issued = true;
+            }
+            if (s >= s_end) continue;  // no segment of this wave-block is both in the window and below the best
+            uint32_t vs[kNC];
+            VarWords<true> v;
+            v.kc = &kc;
+            v.seg_d[0] = v.seg_d[1] = v.seg_d[2] = 0u;
+#pragma unroll
+            for (int j = 0; j < kNC; ++j) {
+                vs[j] = wave_uniform_v(L.wb_begin + o + 64u * j, L.rbits, L.base_tb);
+                var_words<SH>(v, j, vs[j], loff, 0u);
+                w0km_fill<W0>(v, j, L);
+            }
+            uint32_t xin[4][kNC], p[kNC];
+            seg_invariants<NBLK, W0, SH>(xin, p, L, v);
+            for (; s < s_end; ++s) {
+                v.seg_d[0] = s;
+#if DPOW_SI_VSEG
+                {
+                    const uint32_t d[3] = {s, 0u, 0u};
+                    kconst_seg<NBLK, W0, SH, 0, 0, true>(kc, L, d);
+                }
+#endif
+                const uint64_t g = hash_wave_block_si<NBLK, W0, SH>(L, kc, xin, p, v, vs, s, o, lane, loff);
+                if (g != kNoHitG) {  // later segments of this wave-block lie above it
+                    best = g < best ? g : best;
+                    lim = seg_limit_of(L, best);
+                    s_end = s;
+                }
+                if (--pc == 0u) {
+                    pc = L.poll_wb;
+                    const bool lower = best_seen < best;
+                    best = lower ? best_seen : best;
+                    stop = stop_seen;
+                    best_seen = __hip_atomic_load(&L.ctrl->best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    stop_seen = __hip_atomic_load(&L.ctrl->stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (lower) {
+                        lim = seg_limit_of(L, best);
+                        const uint32_t e = seg_limit_at(lim, o);
+                        s_end = e < s_end ? e : s_end;
+                    }
+                    if (stop != 0u) s_end = s;
+                }
+            }
+        }
+        if (stop != 0u || over || !issued) break;
+        claim = claim_take(next_v, x, 0);
+    }
+    // (a claim atomic may still be in flight: search_body)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint32_t prev = __hip_atomic_fetch_add(&L.ctrl->done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (prev + 1u == L.done_target) publish(L.ctrl, L.snap, L.seq, L.claim, L.ctrl_next);
+    }
+}
+#define DPOW_SEARCH_BODY(NBLK, W0, SH, EQ, KSPAN) search_body_si<NBLK, W0, SH, EQ>(L)
+#else
+#define DPOW_SEARCH_BODY(NBLK, W0, SH, EQ, KSPAN) search_body<NBLK, W0, SH, EQ, KSPAN>(L)
+#endif
+
 template <int NBLK, int W0, int SH, bool EQ, bool KSPAN>
 __global__ void __launch_bounds__(kBlockThreads) __attribute__((amdgpu_num_sgpr(DPOW_NUM_SGPR)))
 md5_search_kernel(const Launch L) {
-    search_body<NBLK, W0, SH, EQ, KSPAN>(L);
+    DPOW_SEARCH_BODY(NBLK, W0, SH, EQ, KSPAN);
 }
 
 template <int NBLK, int W0, int SH, bool EQ, bool KSPAN>
 __global__ void __launch_bounds__(kBlockThreads) __attribute__((amdgpu_num_sgpr(DPOW_NUM_SGPR_LONG)))
 md5_search_kernel_lsgpr(const Launch L) {
-    search_body<NBLK, W0, SH, EQ, KSPAN>(L);
+    DPOW_SEARCH_BODY(NBLK, W0, SH, EQ, KSPAN);
 }
 
 template <int NBLK, int W0, int SH, bool EQ, bool KSPAN>
 __global__ void __launch_bounds__(kBlockThreads) __attribute__((amdgpu_num_sgpr(DPOW_NUM_SGPR_W15)))
 md5_search_kernel_w15sgpr(const Launch L) {
-    search_body<NBLK, W0, SH, EQ, KSPAN>(L);
+    DPOW_SEARCH_BODY(NBLK, W0, SH, EQ, KSPAN);
 }
 
 }  // namespace DPOW_KNS

@@ -34,7 +34,18 @@ constexpr KernelFn kernel_of() {
 // has one; other layouts have one kernel for both.
 #define DPOW_K(w, e, nar) \
     kernel_of<DPOW_VNBLK, w, DPOW_VSH, e, !(DPOW_VSH == 3 && nar && narrow_knobs(DPOW_VNBLK, w).on)>()
-#if DPOW_VNBLK == 1
+#if DPOW_VSI
+// The segment-inner unit: one final block, SH = 0, the D-equality test, W0 <= 3 (nonces of 0, 4,
+// 8 and 12 bytes): the invariants cost ~10 VGPRs more per W0 of compiler-scheduled lead-in, and
+// from W0 = 4 on the kernels pass the 72-VGPR cap of VgprK (73-78).
+#if DPOW_VNBLK != 1 || DPOW_VSH != 0
+#error "the segment-inner unit is built for NBLK = 1, SH = 0"
+#endif
+constexpr int kW0Lo = 0;
+const KernelFn kTable[1][1][4] = {
+    {{DPOW_K(0, true, false), DPOW_K(1, true, false), DPOW_K(2, true, false), DPOW_K(3, true, false)}}};
+#define DPOW_ROW(e, n)
+#elif DPOW_VNBLK == 1
 constexpr int kW0Lo = 0;
 #define DPOW_ROW(e, n)                                                                                              \
     {DPOW_K(0, e, n), DPOW_K(1, e, n), DPOW_K(2, e, n),  DPOW_K(3, e, n),  DPOW_K(4, e, n),  DPOW_K(5, e, n),        \
@@ -54,12 +65,17 @@ constexpr int kW0N = sizeof(kTable[0][0]) / sizeof(kTable[0][0][0]);
 
 // narrow: the launch's R >= 64 (rbits >= 6), so no wave-block's lanes span two k
 KernelFn pick(int w0, bool eq, bool narrow) {
+#if DPOW_VSI
+    return eq && w0 >= kW0Lo && w0 < kW0Lo + kW0N ? kTable[0][0][w0 - kW0Lo] : nullptr;
+#endif
     return (w0 >= kW0Lo && w0 < kW0Lo + kW0N) ? kTable[eq ? 1 : 0][narrow ? 1 : 0][w0 - kW0Lo] : nullptr;
 }
 }  // namespace
 
 #if DPOW_VLS  // the chunk-length-spanning SH = 0 kernels: variant_launch_<n>_0_ls
 #define DPOW_SFX _ls
+#elif DPOW_VSI  // the segment-inner kernels: variant_launch_1_0_si
+#define DPOW_SFX _si
 #else
 #define DPOW_SFX
 #endif
@@ -91,7 +107,7 @@ hipError_t DPOW_NAME(variant_prepare_, DPOW_VNBLK, DPOW_VSH)() {
 }
 
 hipError_t DPOW_NAME(variant_occupancy_, DPOW_VNBLK, DPOW_VSH)(int w0, int *blocks_per_cu) {
-    KernelFn fn = pick(w0, false, true);  // the sweep's (workerBits 0) kernel
+    KernelFn fn = pick(w0, DPOW_VSI != 0, true);  // the sweep's (workerBits 0) kernel
     if (!fn) return hipErrorInvalidValue;
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, reinterpret_cast<const void *>(fn),
                                                         kBlockThreads, 0);

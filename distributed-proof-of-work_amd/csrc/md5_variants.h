@@ -21,6 +21,7 @@ DPOW_DECL_VARIANT(2, 2)
 DPOW_DECL_VARIANT(2, 3)
 DPOW_DECL_VARIANT(1, 0_ls)  // chunk-length-spanning SH = 0 kernels (launches below k = 2^24)
 DPOW_DECL_VARIANT(2, 0_ls)
+DPOW_DECL_VARIANT(1, 0_si)  // segment-inner kernels (Launch::n_seg != 0): one block, SH = 0, D-equality
 #undef DPOW_DECL_VARIANT
 
 // True when a kernel variant exists for (nblk, w0, sh).
@@ -34,6 +35,10 @@ inline bool variant_exists(int nblk, int w0, int sh) {
 // Launches whose template is chunk length 0's (L.seg0 == kLsegBase: SH = 0 below k = 2^24)
 // run the "_ls" kernels.  (No timing events: the kernel stamps its start and end into its
 // completion record.)
+// True when a segment-inner kernel exists for the layout (md5_search_kernel.h search_body_si).
+inline bool seg_inner_exists(int nblk, int w0, int sh) {
+    return w0 >= 0 && seg_inner_layout((uint32_t)nblk, (uint32_t)w0, (uint32_t)sh);
+}
 hipError_t search_launch(int nblk, int w0, int sh, const Launch &L, uint32_t grid, hipStream_t stream);
 hipError_t search_occupancy(int nblk, int w0, int sh, int *blocks_per_cu);
 // Load and resolve every search kernel (all layouts, the "_ls" ones, the k = 0 and init

@@ -207,8 +207,17 @@ int plan_window(const uint8_t *nonce, size_t nonce_len, uint32_t ntz, uint32_t w
 void candidate_words(const PlannedLaunch &pl, uint64_t local_idx, uint32_t words[32]) {
     const Launch &Lh = pl.L;
     for (uint32_t w = 0; w < 16 * pl.info.nblk; ++w) words[w] = Lh.T[w];
-    const uint64_t i0 = local_idx & ~63ull;
+    uint64_t i0 = local_idx & ~63ull;
     const uint32_t lane = (uint32_t)(local_idx & 63u);
+    uint32_t seg_of_idx = (uint32_t)((local_idx >> Lh.rbits) >> 24);
+    if (Lh.n_seg != 0u) {
+        // segment-inner (md5_search_kernel.h search_body_si): V from the wave-block's offset in
+        // the first segment's range, the segment word from the segment's number in the launch
+        const uint32_t segbits = 24u + Lh.rbits;
+        const uint64_t rel = i0 - Lh.wb_begin;
+        i0 = Lh.wb_begin + (rel & ((1ull << segbits) - 1ull));
+        seg_of_idx = Lh.seg_first + (uint32_t)(rel >> segbits);
+    }
     const uint32_t V = wave_uniform_v(i0, Lh.rbits, Lh.base_tb) + lane_offset(Lh.rbits, lane);
     const uint32_t sh = pl.info.sh, w0 = pl.info.w0;
     words[w0] += V << (8 * sh);
@@ -228,7 +237,7 @@ void candidate_words(const PlannedLaunch &pl, uint64_t local_idx, uint32_t words
     }
     {  // the segment words, as the kernel re-derives them (md5_search_kernel.h seg_word)
         uint32_t d1, d2;
-        const uint32_t seg = (uint32_t)((local_idx >> Lh.rbits) >> 24);
+        const uint32_t seg = seg_of_idx;
         seg_word_deltas(Lh.T[w0 + 1], Lh.T[w0 + 2], seg, Lh.seg_first, sh, d1, d2);
         words[w0 + 1] += d1;
         if (sh == 3 && w0 + 2 != 16 * pl.info.nblk - 2) words[w0 + 2] += d2;
@@ -341,6 +350,66 @@ int size_search_launch(PlannedLaunch &pl, uint32_t ntz, uint64_t cus, uint64_t s
                                knobs.cpw ? knobs.cpw : launch_claims_per_wave(ntz, L.rbits));
     if (rc < 0) return rc;
     L.poll_wb = knobs.poll_wb ? knobs.poll_wb : launch_poll_wb(ntz, L.rbits);
+    return 0;
+}
+
+bool seg_inner_select(WindowPlanner &planner, PlannedLaunch &pl, uint32_t ntz, int mode) {
+    constexpr uint64_t kSeg = 1ull << 24;
+    if (mode == 0 || pl.k0 || pl.L.lspan) return false;
+    if (!seg_inner_layout(pl.info.nblk, pl.info.w0, pl.info.sh) || !use_d_equality(pl.info.nblk, ntz)) return false;
+    if (pl.info.k_begin < kSeg || pl.info.k_end - pl.info.k_begin < 2 * kSeg) return false;
+    if (mode < 0) {
+        const uint64_t expect = expected_first_hit(ntz, pl.L.rbits);
+        if (expect != ~0ull) {
+            const uint64_t max_seg = ((expect / kSegInnerShare) >> pl.L.rbits) / kSeg;
+            if (max_seg < 2) return false;
+            if (pl.info.k_end - pl.info.k_begin > max_seg * kSeg) {
+                planner.restart(pl.info.k_begin, max_seg * kSeg);
+                planner.next(pl);
+            }
+        }
+    }
+    return true;
+}
+
+int seg_inner_size(PlannedLaunch &pl, uint64_t max_blocks, uint64_t *worker_blocks_out) {
+    Launch &L = pl.L;
+    constexpr uint64_t wpb = kBlockThreads / 64;
+    const uint32_t segbits = 24u + L.rbits;
+    const uint64_t seg_lo = pl.info.k_begin >> 24, seg_hi = (pl.info.k_end - 1) >> 24;
+    const uint64_t n_seg = seg_hi - seg_lo + 1;
+    if (n_seg < 2 || n_seg > 0xFFFFFFFFull || L.seg_first != (uint32_t)seg_lo) return DPOW_EINVAL;
+    L.n_seg = (uint32_t)n_seg;
+    L.wb_begin = seg_lo << segbits;
+    L.n_wblocks = (1ull << segbits) / (uint64_t)kWaveBlock;
+    // a claim's work is chunk wave-blocks in each of n_seg segments: as much as the sized claim's
+    uint64_t chunk = L.chunk / n_seg, chunk_tail = L.chunk_tail / n_seg;
+    while (chunk & (chunk - 1)) chunk &= chunk - 1;
+    while (chunk_tail & (chunk_tail - 1)) chunk_tail &= chunk_tail - 1;
+    if (chunk < 1) chunk = 1;
+    if (chunk_tail < 1) chunk_tail = 1;
+    if (chunk_tail > chunk) chunk_tail = chunk;
+    uint64_t worker_blocks = (L.n_wblocks + wpb - 1) / wpb;
+    if (worker_blocks > max_blocks) worker_blocks = max_blocks;
+    // the guided tail and the grid, as size_launch cuts them
+    const uint64_t tail_wb = worker_blocks * wpb * kTailClaimsPerWave * chunk_tail;
+    const uint64_t n_big = L.n_wblocks > tail_wb ? (L.n_wblocks - tail_wb) / chunk : 0;
+    const uint64_t rest = L.n_wblocks - n_big * chunk;
+    const uint64_t n_chunks = n_big + (rest + chunk_tail - 1) / chunk_tail;
+    uint64_t need_blocks = (n_chunks + wpb - 1) / wpb;
+    if (need_blocks < n_chunks && need_blocks < kClaimCounters)
+        need_blocks = n_chunks < kClaimCounters ? n_chunks : kClaimCounters;
+    if (worker_blocks > need_blocks) worker_blocks = need_blocks;
+    const uint64_t min_blocks = n_chunks < kClaimCounters ? n_chunks : kClaimCounters;
+    if (worker_blocks < min_blocks && min_blocks <= max_blocks) worker_blocks = min_blocks;
+    if (worker_blocks < kClaimCounters && worker_blocks < n_chunks) return DPOW_EINVAL;
+    L.chunk = (uint32_t)chunk;
+    L.chunk_tail = (uint32_t)chunk_tail;
+    L.n_big = n_big;
+    L.n_chunks = n_chunks;
+    L.n_head = 2 * worker_blocks * wpb;
+    L.n_static = 0;
+    *worker_blocks_out = worker_blocks;
     return 0;
 }
 

@@ -211,6 +211,7 @@ uint64_t launch_blocks_per_cu(uint64_t candidates, uint32_t ntz, uint32_t rbits,
 // (the DPOW_DIAG_* A/B environment of dpow_open).
 struct LaunchKnobs {
     uint32_t bpc = 0, min_chunk = 0, cpw = 0, poll_wb = 0;
+    int seg_inner = -1;            // segment-inner launches: -1 the policy, 0 never, 1 wherever the shape permits
     uint32_t share_launch_us = 0;  // launch length on a shared device (kShareLaunchNs)
     uint32_t share_max = 0;        // grid share cap (kShareMax)
 };
@@ -257,6 +258,26 @@ constexpr int64_t kRecentNs = 100 * 1000 * 1000;
 constexpr int64_t kShareLaunchNs = (int64_t)DPOW_SHARE_LAUNCH_US * 1000;
 constexpr double kEstRate = 2.3e11;  // candidates/s of one device (bench: 217-218 on the one-block layouts)
 uint64_t grid_share(uint64_t active, const LaunchKnobs &knobs);
+
+// Segment-inner launches (md5_search_kernel.h search_body_si): a wave keeps its wave-block and
+// walks the launch's 2^24-k segments, so the work that depends on word W0 alone is done once
+// per wave-block instead of once per candidate (about 2 % fewer VALU instructions).  The price:
+// a hit is found out of index order, so the launch drains whole -- at most one launch of extra
+// hashing per search.  A launch runs segment-inner when
+//   - its layout has such a kernel (seg_inner_layout) and ntz >= 8 (the D-equality test),
+//   - it lies at k >= 2^24 and is at least 2 * 2^24 k long, and
+//   - it is at most 1 / kSegInnerShare of the partition's expected first hit: the saving is ~2 %
+//     of the hashing up to the hit, the worst-case loss one launch = 1 / 64 = 1.6 % of it.  A
+//     longer launch is cut to that length (restart), whole segments: N >= 14 and the sweep are
+//     unlimited, N = 10 runs launches of 4 segments, N <= 9 never qualifies (less than 2).
+// seg_inner_select (before the launch is sized) applies the rule, re-planning pl when it cuts;
+// seg_inner_size (after size_search_launch) re-cuts the sized claims over ONE segment's
+// wave-blocks: Launch::n_seg segments, wb_begin / n_wblocks a segment's range, chunks of
+// chunk / n_seg wave-blocks (at least 1) so a claim stays about as much work as before.
+// mode: LaunchKnobs::seg_inner.
+constexpr uint64_t kSegInnerShare = 64;
+bool seg_inner_select(WindowPlanner &planner, PlannedLaunch &pl, uint32_t ntz, int mode);
+int seg_inner_size(PlannedLaunch &pl, uint64_t max_blocks, uint64_t *worker_blocks);
 // Re-plans pl (the launch planner.next() last returned) to at most kShareLaunchNs of hashing
 // when active > 1; returns whether it did.
 bool cap_shared_launch(WindowPlanner &planner, PlannedLaunch &pl, uint64_t active, const LaunchKnobs &knobs);

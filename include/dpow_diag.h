@@ -72,11 +72,30 @@ typedef struct dpow_diag_launch {
     uint32_t wave_block;          /* local indices per wave-block */
     uint64_t n_static;            /* claims handed out by wave index (the "_ls" kernels' static first claims) */
     uint32_t poll_wb;             /* wave-blocks per poll group */
-    uint32_t pad;
+    uint32_t n_seg;               /* != 0: dpow_search runs the launch segment-inner over this many 2^24-k
+                                   * segments (plan.h seg_inner_select) and re-cuts its claims over one
+                                   * segment's wave-blocks; dpow_diag_launch_geometry still reports them as
+                                   * sized in index order, dpow_diag_seg_inner_geometry as the kernel gets them */
 } dpow_diag_launch;
 int dpow_diag_launch_geometry(const uint8_t *nonce, size_t nonce_len, uint32_t ntz, uint32_t worker_byte,
                               uint32_t worker_bits, uint64_t k_begin, uint64_t k_end, uint32_t cus,
                               uint32_t share, dpow_diag_launch *out, size_t max_launches);
+
+/* The same for segment-inner launches, as their kernel gets them: wb_begin is the first
+ * segment's first index, n_wblocks one segment's wave-blocks, the claims cover those, and a
+ * wave hashes each wave-block in every one of the n_seg segments (md5_search_kernel.h
+ * search_body_si).  mode: -1 the search's policy, 0 never, 1 wherever the shape permits
+ * (the DPOW_DIAG_SEG_INNER environment knob of dpow_open).  The device is not shared. */
+int dpow_diag_seg_inner_geometry(const uint8_t *nonce, size_t nonce_len, uint32_t ntz, uint32_t worker_byte,
+                                 uint32_t worker_bits, uint64_t k_begin, uint64_t k_end, uint32_t cus, int mode,
+                                 dpow_diag_launch *out, size_t max_launches);
+/* dpow_plan_candidate for local index `local_idx` of the window's launch that holds it, planned
+ * as above: the words as that launch's kernel assembles them.  Returns 1 if the launch is
+ * segment-inner, 0 if not, < 0 on error. */
+int dpow_diag_seg_inner_candidate(const uint8_t *nonce, size_t nonce_len, uint32_t ntz, uint32_t worker_byte,
+                                  uint32_t worker_bits, uint64_t k_begin, uint64_t k_end, int mode,
+                                  uint64_t local_idx, uint32_t iv_out[4], uint32_t words_out[32],
+                                  uint32_t *nblk_out);
 
 /* Worker workgroups per CU dpow_search gives a launch of `candidates` local indices
  * at (ntz, worker_bits) on a device it has alone (plan.cpp launch_blocks_per_cu): 6 (the
@@ -96,7 +115,8 @@ uint64_t dpow_diag_blocks_per_cu(uint64_t candidates, uint32_t ntz, uint32_t wor
  * per poll group), DPOW_DIAG_BPC (worker workgroups per CU), DPOW_DIAG_MIN_CHUNK (minimum
  * wave-blocks per claim, a power of two), DPOW_DIAG_CPW (big claims per wave: the chunk
  * sizing), DPOW_DIAG_SHARE_LAUNCH_US (launch length while the device is shared),
- * DPOW_DIAG_SHARE_MAX (grid share cap).  Returns 0, or < 0 on error. */
+ * DPOW_DIAG_SHARE_MAX (grid share cap), DPOW_DIAG_SEG_INNER (0: no segment-inner launch, 1:
+ * wherever the shape permits; unset: the policy of plan.h seg_inner_select).  Returns 0, or < 0 on error. */
 int dpow_diag_search_times(struct dpow_ctx *ctx, int64_t out[8]);
 
 /* The launches of the context's last dpow_search call, in launch order (round 5): the
@@ -109,7 +129,7 @@ int dpow_diag_search_times(struct dpow_ctx *ctx, int64_t out[8]);
  * or < 0 on error.  dpow_diag_clock_sync maps the device stamps to host time. */
 typedef struct dpow_diag_launch_time {
     uint64_t seq;                 /* launch sequence number of the context */
-    int32_t kind;                 /* 0 the k = 0 kernel, 1 an md5 launch */
+    int32_t kind;                 /* 0 the k = 0 kernel, 1 an md5 launch, 2 a segment-inner md5 launch */
     int32_t recorded;             /* its completion record is written */
     int64_t queued_ns, seen_ns;   /* host: queued, record consumed (-1: not) */
     uint64_t t_start_tick, t_end_tick;  /* device s_memrealtime stamps of the record */

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Device-only disassembly of every kernel translation unit of libdpow.so (the 8 (NBLK, SH) units,
-# the 2 chunk-length-spanning units, search_ctrl.hip), one .s per unit, into DIR: a refactor of
+# the 2 chunk-length-spanning units, the segment-inner unit, search_ctrl.hip), one .s per unit, into DIR: a refactor of
 # the kernel sources that claims to change nothing is checked by diffing two dumps.
 #   bash tools/isa_dump.sh DIR [extra hipcc flags]
 set -e
@@ -22,5 +22,6 @@ for v in 1_0 1_1 1_2 1_3 2_0 2_1 2_2 2_3; do
 done
 unit ls1_0 md5_variant.hip -DDPOW_VLS=1 -DDPOW_VNBLK=1 -DDPOW_VSH=0 "$@" &
 unit ls2_0 md5_variant.hip -DDPOW_VLS=1 -DDPOW_VNBLK=2 -DDPOW_VSH=0 "$@" &
+unit si1_0 md5_variant.hip -DDPOW_VSI=1 -DDPOW_VNBLK=1 -DDPOW_VSH=0 "$@" &
 unit ctrl search_ctrl.hip "$@" &
 wait

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Static ISA check of the search kernel's hash loop (no GPU needed).
 
-    python tools/isa_loop.py [--csrc DIR] [--nblk 1] [--sh 0] [--w0 1,0,2,3,13] [-- extra hipcc flags]
+    python tools/isa_loop.py [--csrc DIR] [--nblk 1] [--sh 0] [--w0 1,0,2,3,13] [--si] [-- extra hipcc flags]
 
 Compiles one md5_variant.hip translation unit for gfx950, disassembles it and,
 for each md5_search_kernel<NBLK, W0, SH>, finds the hash loop (the region the
@@ -9,6 +9,10 @@ longest backward branch closes) and prints its instruction mix: VALU by opcode,
 SALU, and SGPR-spill traffic (v_readlane/v_writelane) inside the loop.  Spill
 reloads in the loop cost issue slots on every wave-block; the SGPR budget
 (DPOW_NUM_SGPR) and the Launch layout decide whether the compiler needs them.
+
+--si: the segment-inner unit (-DDPOW_VSI=1: NBLK = 1, SH = 0, W0 <= 3, D-equality).  Its hash
+block is one segment's hash of a wave-block; seg_loop_mix() is the segment loop around it (the
+smallest loop that holds the hash block), which must stay free of spill reloads too.
 """
 import argparse
 import collections
@@ -107,6 +111,32 @@ def loop_mix(lines):
     return lo - base, hi - base, collections.Counter(body)
 
 
+def seg_loop_mix(lines):
+    """The smallest backward-branch loop containing the longest straight-line run: the
+    segment loop of the segment-inner kernels (offsets, instruction mix)."""
+    ins = []
+    for l in lines:
+        m = re.search(r"//\s*([0-9A-F]{6,}):", l)
+        if m:
+            ins.append((int(m.group(1), 16), l.split()[0], l))
+    blocks = hash_block_mix(lines)
+    if not ins or not blocks:
+        return None
+    base = ins[0][0]
+    lo, hi, _ = max(blocks, key=lambda b: sum(b[2].values()))
+    best = None
+    for a, mn, l in ins:
+        m = re.search(r"<[^+>]*\+0x([0-9a-f]+)>", l)
+        if "branch" not in mn or not m:
+            continue
+        tgt = int(m.group(1), 16)
+        if tgt <= lo and a - base >= hi and (best is None or a - base - tgt < best[1] - best[0]):
+            best = (tgt, a - base)
+    if best is None:
+        return None
+    return best[0], best[1], collections.Counter(mn for a, mn, _ in ins if best[0] <= a - base <= best[1])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--csrc", default=os.path.join(ROOT, "distributed-proof-of-work_amd", "csrc"))
@@ -115,10 +145,11 @@ def main():
     ap.add_argument("--w0", default="1,0,2,3,13")
     ap.add_argument("--eq", type=int, default=None, help="1: D-equality kernels (default for --nblk 1)")
     ap.add_argument("--kspan", type=int, default=0, help="SH = 3: 0 = the narrow (R >= 64) kernel, 1 = the general one")
+    ap.add_argument("--si", action="store_true", help="the segment-inner unit (-DDPOW_VSI=1)")
     ap.add_argument("--verbose", action="store_true")
     ap.add_argument("extra", nargs="*")
     a = ap.parse_args()
-    text = disasm(a.csrc, a.nblk, a.sh, a.extra)
+    text = disasm(a.csrc, a.nblk, a.sh, a.extra + (["-DDPOW_VSI=1"] if a.si else []))
     eq = (1 if a.nblk == 1 else 0) if a.eq is None else a.eq
     for w0 in [int(x) for x in a.w0.split(",")]:
         kl = kernel_lines(text, a.nblk, w0, a.sh, eq, a.kspan)
@@ -131,6 +162,10 @@ def main():
             if a.verbose:
                 for k, v in c.most_common():
                     print(f"    {v:5d} {k}")
+        if a.si and kl:
+            lo, hi, c = seg_loop_mix(kl)
+            print(f"    segment loop +0x{lo:x}..+0x{hi:x}: spill readlane/writelane "
+                  f"{c.get('v_readlane_b32', 0) + c.get('v_writelane_b32', 0)} (rare paths included)")
         r = loop_mix(kl)
         if r is None:
             print(f"<{a.nblk},{w0},{a.sh}>: no loop found")
