@@ -17,10 +17,23 @@
  * writes any new vector.  It never ships to the GPU box and nothing in the
  * product loads it.
  *
+ * Nonces of 64 bytes and more: the whole nonce-only blocks are hashed by plain
+ * scalar code (md5_block) into a midstate; the vectorised final block starts
+ * from it, holds the nonce's last nonce_len mod 64 bytes and carries the bit
+ * length of the whole message.  One final block must do:
+ * nonce_len mod 64 + 1 + chunk length + 9 <= 64.
+ *
+ * All-hits mode (a sixth argument "all"): no best-so-far pruning; every
+ * candidate of the window whose digest ends in >= ntz '0' characters is
+ * collected with its actual trailing-'0' count and printed sorted by global
+ * index.  gen_golden.py --seg-inner cross-checks this mode against the byte-wise
+ * oracle walked hit by hit before it writes a list.
+ *
  * Build (gen_golden.py does this): gcc -O3 -mavx512f -fopenmp-free:
  *   gcc -O3 -march=native -pthread -o fast_scan fast_scan.c
- * Usage: fast_scan <nonce-hex> <ntz> <k_begin> <k_end> <threads>
- *   prints "hit <global_idx>" or "none".
+ * Usage: fast_scan <nonce-hex> <ntz> <k_begin> <k_end> <threads> [all]
+ *   prints "hit <global_idx>" or "none"; with "all", one "hit <global_idx> <tz>"
+ *   line per hit in index order, then "end <count>".
  */
 #include <immintrin.h>
 #include <pthread.h>
@@ -42,8 +55,18 @@ static const uint32_t T[64] = {
 #define NV 4 /* independent 16-lane vectors per step: 64 thread bytes */
 
 typedef struct {
-    uint8_t nonce[64];
+    uint64_t g;
+    unsigned tz;
+} hit_t;
+
+typedef struct {
+    uint8_t nonce[1024];
     size_t nonce_len;
+    uint32_t iv[4]; /* MD5 state after the nonce's whole 64-byte blocks */
+    int all;        /* all-hits mode */
+    pthread_mutex_t lock;
+    hit_t *hits;
+    size_t nhits, cap;
     unsigned ntz;
     uint64_t k_begin, k_end, unit;
     uint32_t mask[4]; /* required-zero bits of digest words A, B, C, D */
@@ -69,6 +92,59 @@ static void tail_masks(unsigned ntz, uint32_t m[4]) {
     }
 }
 
+static const int S[4][4] = {{7, 12, 17, 22}, {5, 9, 14, 20}, {4, 11, 16, 23}, {6, 10, 15, 21}};
+
+/* RFC 1321 compression of one 64-byte block, plain scalar code (the midstate of long nonces). */
+static void md5_block(uint32_t st[4], const uint8_t *blk) {
+    uint32_t M[16], a = st[0], b = st[1], c = st[2], d = st[3];
+    for (int w = 0; w < 16; ++w)
+        M[w] = (uint32_t)blk[4 * w] | ((uint32_t)blk[4 * w + 1] << 8) | ((uint32_t)blk[4 * w + 2] << 16) |
+               ((uint32_t)blk[4 * w + 3] << 24);
+    for (int i = 0; i < 64; ++i) {
+        uint32_t f;
+        int g;
+        if (i < 16) f = (b & c) | (~b & d), g = i;
+        else if (i < 32) f = (d & b) | (~d & c), g = (5 * i + 1) & 15;
+        else if (i < 48) f = b ^ c ^ d, g = (3 * i + 5) & 15;
+        else f = c ^ (b | ~d), g = (7 * i) & 15;
+        const uint32_t t = a + f + M[g] + T[i];
+        const int s = S[i / 16][i % 4];
+        a = d, d = c, c = b;
+        b += (t << s) | (t >> (32 - s));
+    }
+    st[0] += a, st[1] += b, st[2] += c, st[3] += d;
+}
+
+/* Trailing '0' characters of the hex digest: byte 15 low nibble, high nibble, byte 14 ... */
+static unsigned hex_trailing_zeroes(const uint32_t w[4]) {
+    unsigned n = 0;
+    for (int byte = 15; byte >= 0; --byte) {
+        const uint8_t v = (uint8_t)(w[byte / 4] >> (8 * (byte % 4)));
+        if (v & 0x0F) return n;
+        ++n;
+        if (v >> 4) return n;
+        ++n;
+    }
+    return n;
+}
+
+static void add_hit(job_t *j, uint64_t g, unsigned tz) {
+    pthread_mutex_lock(&j->lock);
+    if (j->nhits == j->cap) {
+        j->cap = j->cap ? 2 * j->cap : 1024;
+        j->hits = (hit_t *)realloc(j->hits, j->cap * sizeof *j->hits);
+        if (!j->hits) abort();
+    }
+    j->hits[j->nhits].g = g;
+    j->hits[j->nhits++].tz = tz;
+    pthread_mutex_unlock(&j->lock);
+}
+
+static int cmp_hit(const void *a, const void *b) {
+    const uint64_t x = ((const hit_t *)a)->g, y = ((const hit_t *)b)->g;
+    return x < y ? -1 : x > y;
+}
+
 #define ROL(x, s) _mm512_rol_epi32((x), (s))
 /* F, G, H, I as ternary-logic truth tables over (b, c, d) */
 #define TF 0xCA
@@ -89,22 +165,23 @@ static void tail_masks(unsigned ntz, uint32_t m[4]) {
 
 static void *scan_worker(void *arg) {
     job_t *j = (job_t *)arg;
-    const size_t p = j->nonce_len; /* byte offset of the thread byte */
+    const size_t p = j->nonce_len % 64; /* byte offset of the thread byte in the final block */
+    const uint8_t *tail = j->nonce + (j->nonce_len - p);
     const __m512i lane = _mm512_set_epi32(15, 14, 13, 12, 11, 10, 9, 8, 7, 6, 5, 4, 3, 2, 1, 0);
     for (;;) {
         const uint64_t u = __atomic_fetch_add(&j->next_unit, 1, __ATOMIC_RELAXED);
         const uint64_t k0 = j->k_begin + u * j->unit;
-        if (k0 >= j->k_end || k0 * 256u >= load_best(j)) return NULL;
+        if (k0 >= j->k_end || (!j->all && k0 * 256u >= load_best(j))) return NULL;
         const uint64_t k1 = k0 + j->unit < j->k_end ? k0 + j->unit : j->k_end;
         for (uint64_t k = k0; k < k1; ++k) {
             uint8_t buf[64];
             memset(buf, 0, sizeof buf);
-            memcpy(buf, j->nonce, p);
+            memcpy(buf, tail, p);
             size_t clen = 0;
             for (uint64_t x = k; x; x >>= 8) buf[p + 1 + clen++] = (uint8_t)(x & 0xFF);
             const size_t len = p + 1 + clen;
             buf[len] = 0x80;
-            const uint64_t bits = (uint64_t)len * 8u;
+            const uint64_t bits = (uint64_t)(j->nonce_len - p + len) * 8u;
             for (int b = 0; b < 8; ++b) buf[56 + b] = (uint8_t)(bits >> (8 * b));
             uint32_t M[16];
             for (int w = 0; w < 16; ++w)
@@ -121,12 +198,11 @@ static void *scan_worker(void *arg) {
                 }
                 __m512i a[NV], b[NV], c[NV], d[NV];
                 for (int v = 0; v < NV; ++v) {
-                    a[v] = _mm512_set1_epi32(0x67452301);
-                    b[v] = _mm512_set1_epi32((int)0xefcdab89);
-                    c[v] = _mm512_set1_epi32((int)0x98badcfe);
-                    d[v] = _mm512_set1_epi32(0x10325476);
+                    a[v] = _mm512_set1_epi32((int)j->iv[0]);
+                    b[v] = _mm512_set1_epi32((int)j->iv[1]);
+                    c[v] = _mm512_set1_epi32((int)j->iv[2]);
+                    d[v] = _mm512_set1_epi32((int)j->iv[3]);
                 }
-                static const int S[4][4] = {{7, 12, 17, 22}, {5, 9, 14, 20}, {4, 11, 16, 23}, {6, 10, 15, 21}};
 #define R4(tt, r, i0, w0, w1, w2, w3)                       \
     STEP(a, b, c, d, tt, mv[w0], i0 + 0, S[r][0]);          \
     STEP(d, a, b, c, tt, mv[w1], i0 + 1, S[r][1]);          \
@@ -142,15 +218,26 @@ static void *scan_worker(void *arg) {
                 R4(TI, 3, 60, 4, 11, 2, 9)
 #undef R4
                 for (int v = 0; v < NV; ++v) {
-                    const __m512i A = _mm512_add_epi32(a[v], _mm512_set1_epi32(0x67452301));
-                    const __m512i B = _mm512_add_epi32(b[v], _mm512_set1_epi32((int)0xefcdab89));
-                    const __m512i C = _mm512_add_epi32(c[v], _mm512_set1_epi32((int)0x98badcfe));
-                    const __m512i D = _mm512_add_epi32(d[v], _mm512_set1_epi32(0x10325476));
+                    const __m512i A = _mm512_add_epi32(a[v], _mm512_set1_epi32((int)j->iv[0]));
+                    const __m512i B = _mm512_add_epi32(b[v], _mm512_set1_epi32((int)j->iv[1]));
+                    const __m512i C = _mm512_add_epi32(c[v], _mm512_set1_epi32((int)j->iv[2]));
+                    const __m512i D = _mm512_add_epi32(d[v], _mm512_set1_epi32((int)j->iv[3]));
                     __mmask16 z = _mm512_testn_epi32_mask(D, _mm512_set1_epi32((int)j->mask[3]));
                     if (j->mask[2]) z &= _mm512_testn_epi32_mask(C, _mm512_set1_epi32((int)j->mask[2]));
                     if (j->mask[1]) z &= _mm512_testn_epi32_mask(B, _mm512_set1_epi32((int)j->mask[1]));
                     if (j->mask[0]) z &= _mm512_testn_epi32_mask(A, _mm512_set1_epi32((int)j->mask[0]));
-                    if (z) {
+                    if (z && j->all) {
+                        uint32_t wa[16], wb[16], wc[16], wd[16];
+                        _mm512_storeu_si512(wa, A);
+                        _mm512_storeu_si512(wb, B);
+                        _mm512_storeu_si512(wc, C);
+                        _mm512_storeu_si512(wd, D);
+                        for (unsigned l = 0; l < 16; ++l) {
+                            if (!((z >> l) & 1)) continue;
+                            const uint32_t w[4] = {wa[l], wb[l], wc[l], wd[l]};
+                            add_hit(j, k * 256u + 16u * (NV * rep + v) + l, hex_trailing_zeroes(w));
+                        }
+                    } else if (z) {
                         const unsigned tbyte = 16u * (NV * rep + v) + (unsigned)__builtin_ctz(z);
                         set_best(j, k * 256u + tbyte);
                         goto next_unit; /* later thread bytes / k of this unit hold larger indices */
@@ -163,15 +250,15 @@ static void *scan_worker(void *arg) {
 }
 
 int main(int argc, char **argv) {
-    if (argc != 6) {
-        fprintf(stderr, "usage: %s <nonce-hex> <ntz> <k_begin> <k_end> <threads>\n", argv[0]);
+    if (argc != 6 && !(argc == 7 && !strcmp(argv[6], "all"))) {
+        fprintf(stderr, "usage: %s <nonce-hex> <ntz> <k_begin> <k_end> <threads> [all]\n", argv[0]);
         return 2;
     }
     static job_t j;
     const char *hx = argv[1];
     j.nonce_len = strlen(hx) / 2;
-    if (j.nonce_len + 1 + 5 + 9 > 64) {
-        fprintf(stderr, "fast_scan: one-block messages only (nonce <= 49 bytes)\n");
+    if (j.nonce_len > sizeof j.nonce) {
+        fprintf(stderr, "fast_scan: nonce longer than %zu bytes\n", sizeof j.nonce);
         return 2;
     }
     for (size_t i = 0; i < j.nonce_len; ++i) sscanf(hx + 2 * i, "%2hhx", &j.nonce[i]);
@@ -179,7 +266,20 @@ int main(int argc, char **argv) {
     j.k_begin = strtoull(argv[3], NULL, 0);
     j.k_end = strtoull(argv[4], NULL, 0);
     const int nth = atoi(argv[5]);
-    if (j.k_end > (1ull << 40)) return 2;
+    j.all = argc == 7;
+    if (j.k_end > (1ull << 55) - 1 || j.k_begin > j.k_end) {
+        fprintf(stderr, "fast_scan: bad k window (k < 2^55 - 1)\n");
+        return 2;
+    }
+    size_t clen_max = 0;
+    for (uint64_t x = j.k_end ? j.k_end - 1 : 0; x; x >>= 8) ++clen_max;
+    if (j.nonce_len % 64 + 1 + clen_max + 9 > 64) {
+        fprintf(stderr, "fast_scan: the nonce's tail, thread byte, chunk and padding must fit one block\n");
+        return 2;
+    }
+    j.iv[0] = 0x67452301, j.iv[1] = 0xefcdab89, j.iv[2] = 0x98badcfe, j.iv[3] = 0x10325476;
+    for (size_t b = 0; b + 64 <= j.nonce_len; b += 64) md5_block(j.iv, j.nonce + b);
+    pthread_mutex_init(&j.lock, NULL);
     tail_masks(j.ntz, j.mask);
     j.unit = 1u << 12;
     j.next_unit = 0;
@@ -187,6 +287,12 @@ int main(int argc, char **argv) {
     pthread_t th[256];
     for (int i = 0; i < nth && i < 256; ++i) pthread_create(&th[i], NULL, scan_worker, &j);
     for (int i = 0; i < nth && i < 256; ++i) pthread_join(th[i], NULL);
+    if (j.all) {
+        if (j.nhits) qsort(j.hits, j.nhits, sizeof *j.hits, cmp_hit);
+        for (size_t i = 0; i < j.nhits; ++i) printf("hit %llu %u\n", (unsigned long long)j.hits[i].g, j.hits[i].tz);
+        printf("end %zu\n", j.nhits);
+        return 0;
+    }
     if (j.best == UINT64_MAX) printf("none\n");
     else printf("hit %llu\n", (unsigned long long)j.best);
     return 0;

@@ -25,7 +25,36 @@ Every case is also checked against SURVEY.md Appendix A where the survey lists i
     fresh nonces seeded random.Random(416)" (4 four-byte nonces; SURVEY.md
     section 8(d) item 5), the config-1/2/5 nonces at N = 9, and [1,2,3,4] at N = 10.
 
-Usage:  python tests/golden/gen_golden.py [--big] | --deep
+  * --seg-inner: tests/golden/seg_inner_hits.json, all-hits lists for the
+    segment-inner kernels (md5_search_kernel.h search_body_si).  Each case is
+    {name, nonce, k_begin, k_end, hits: [[g, tz], ...]}: every candidate
+    g = k * 256 + threadByte of the workerBits = 0 window [k_begin, k_end) whose
+    hex digest ends in >= 8 '0' characters, with its actual trailing-'0' count,
+    sorted by g.  One list serves every partition shape: a partition's hits are
+    the entries whose thread byte is in thread_bytes(worker_byte, worker_bits).
+    The windows are whole 2^24-k segments (2^32 candidates, ~1 entry each) for
+    every W0 = (nonce_len mod 64) / 4 the kernels admit, two midstate nonces
+    (64 and 76 bytes), the chunk-length steps at k = 2^40 and 2^48, and the
+    last segments below DPOW_K_LIMIT.  They come from fast_scan.c's all-hits
+    mode.  Before anything is written
+      - all-hits mode is compared with the byte-wise C oracle walked hit by hit
+        (mine_window, and per thread byte inside a k) on small windows at
+        ntz 4-6, at k = 0, at k >= 2^24, across k = 2^32, 2^40 and 2^48 (chunk
+        lengths 4-7) and below DPOW_K_LIMIT, for a 4-, a 12-, a 64- and a
+        76-byte nonce;
+      - first-hit mode must still reproduce every golden of pow_golden.json it
+        can express (workerBits = 0, one final block): first_hits, windows,
+        nonce_lengths (which exercises the midstate) and the N = 9 deep_hits
+        from k = 0; the N = 10 deep hit (1.7e12 candidates from k = 0, which
+        --deep scanned) over the 64 segments that end behind it;
+      - every listed hit's digest is recomputed with hashlib.
+    The generator enforces (and tests/test_seg_inner_golden.py re-checks): every
+    case has >= 4 entries; for each W0 some case has an entry with tz >= 9 behind
+    an entry with tz = 8; w1 holds the N = 9 deep golden as its first tz >= 9
+    entry.  A case that misses is lengthened in 16-segment steps up to 64
+    segments, then its seeded nonce is replaced.
+
+Usage:  python tests/golden/gen_golden.py [--big] | --deep | --seg-inner
 """
 import argparse
 import ctypes
@@ -240,11 +269,223 @@ def deep(path):
             f.write("\n")
 
 
+# ---------------- --seg-inner: all-hits lists for the segment-inner kernels ----------------
+SEG = 1 << 24  # k per segment (md5_search_kernel.h: a segment fixes k >> 24)
+K_LIMIT = (1 << 55) - 1  # include/dpow.h DPOW_K_LIMIT
+SEG_INNER_NTZ = 8
+N9_GOLDEN = 48853296051  # deep_hits: [1,2,3,4], N = 9
+MAX_SEGS = 64
+
+
+def secret_from_index(g):
+    return [g & 0xFF] + chunk_of(g >> 8)
+
+
+def tz_of(nonce, g):
+    h = md5hex(nonce, secret_from_index(g))
+    return len(h) - len(h.rstrip("0"))
+
+
+def fast_scan_window(exe, nonce, ntz, k0, k1, threads=None):
+    """First-hit mode over [k0, k1): global index or None."""
+    import subprocess
+    threads = threads or os.cpu_count() or 8
+    out = subprocess.check_output([exe, bytes(nonce).hex(), str(ntz), str(k0), str(k1), str(threads)]).decode().split()
+    return None if out[0] == "none" else int(out[1])
+
+
+def fast_scan_all(exe, nonce, ntz, k0, k1, threads=None):
+    """All-hits mode over [k0, k1): [[g, tz], ...] sorted by g."""
+    import subprocess
+    threads = threads or os.cpu_count() or 8
+    lines = subprocess.check_output(
+        [exe, bytes(nonce).hex(), str(ntz), str(k0), str(k1), str(threads), "all"]).decode().splitlines()
+    assert lines and lines[-1] == f"end {len(lines) - 1}", lines[-1:]
+    hits = []
+    for ln in lines[:-1]:
+        w = ln.split()
+        assert w[0] == "hit" and len(w) == 3, ln
+        hits.append([int(w[1]), int(w[2])])
+    return hits
+
+
+def oracle_all_hits(lib, nonce, ntz, k0, k1):
+    """The byte-wise oracle walked hit by hit: every hit of the workerBits = 0 window with its
+    trailing-zero count.  Inside the k of a hit the later thread bytes are asked one by one
+    (workerBits = 8: one thread byte per worker); tz is the largest ntz the oracle still accepts."""
+    hits, k = [], k0
+    while k < k1:
+        r = c_mine(lib, nonce, ntz, 0, 0, k, k1)
+        if r is None:
+            break
+        kh = r[1] >> 8
+        for tb in range(r[1] & 0xFF, 256):
+            if c_mine(lib, nonce, ntz, tb, 8, kh, kh + 1) is None:
+                continue
+            tz = ntz
+            while tz < 32 and c_mine(lib, nonce, tz + 1, tb, 8, kh, kh + 1) is not None:
+                tz += 1
+            hits.append([kh * 256 + tb, tz])
+        k = kh + 1
+    return hits
+
+
+def seeded_nonce(seed, length):
+    rnd = random.Random(seed)
+    return [rnd.randrange(256) for _ in range(length)]
+
+
+def seg_inner_crosscheck(exe, lib, golden):
+    """The scanner's new modes against the byte-wise oracle and the existing goldens."""
+    nonces = [[1, 2, 3, 4], seeded_nonce(7012, 12), seeded_nonce(7064, 64), seeded_nonce(7076, 76)]
+    # (ntz, k_begin, k_end): dense hits; k = 0, k >= 2^24, chunk lengths 4|5, 5|6, 6|7, the top
+    wins = [(4, 0, 1 << 13), (5, SEG + 12345, SEG + 12345 + (1 << 15)), (6, 3 * SEG - (1 << 17), 3 * SEG + (1 << 17)),
+            (4, (1 << 32) - 4000, (1 << 32) + 4000), (4, (1 << 40) - 4000, (1 << 40) + 4000),
+            (5, (1 << 48) - 9000, (1 << 48) + 9000), (4, K_LIMIT - (1 << 13), K_LIMIT)]
+    total = 0
+    for nonce in nonces:
+        for ntz, k0, k1 in wins:
+            got = fast_scan_all(exe, nonce, ntz, k0, k1)
+            exp = oracle_all_hits(lib, nonce, ntz, k0, k1)
+            assert got == exp and (got or ntz > 4), (len(nonce), ntz, k0, k1, got[:4], exp[:4])
+            assert all(tz_of(nonce, g) == tz for g, tz in got)
+            total += len(got)
+    print("all-hits mode agrees with the oracle walk on", len(nonces) * len(wins), "windows,", total, "hits",
+          file=sys.stderr)
+
+    def one_block(nonce, k):
+        return len(nonce) % 64 + 1 + len(chunk_of(k)) + 9 <= 64
+
+    n = 0
+    for e in golden["first_hits"] + golden["nonce_lengths"]:
+        k = e["global_idx"] >> 8
+        if not one_block(e["nonce"], k + 1):
+            continue
+        assert fast_scan_window(exe, e["nonce"], e["ntz"], 0, k + 2) == e["global_idx"], e
+        n += 1
+    for e in golden["windows"]:
+        if e["worker_bits"] == 0:
+            assert fast_scan_window(exe, e["nonce"], e["ntz"], e["k_begin"], e["k_end"]) == e["global_idx"], e
+            n += 1
+    for e in golden["deep_hits"]:
+        k = e["global_idx"] >> 8
+        k0 = 0 if e["ntz"] <= 9 else max(0, (k // SEG + 1 - MAX_SEGS) * SEG)
+        assert fast_scan_window(exe, e["nonce"], e["ntz"], k0, k + 2) == e["global_idx"], e
+        n += 1
+    print("first-hit mode reproduces", n, "existing goldens", file=sys.stderr)
+
+
+def _n9_after_8(hits):
+    """An entry with tz >= 9 behind an entry with tz = 8."""
+    seen8 = False
+    for _, tz in hits:
+        if tz == 8:
+            seen8 = True
+        elif seen8 and tz >= 9:
+            return True
+    return False
+
+
+def seg_inner_cases():
+    """name -> (nonce length or the nonce, seed, window(extra) with extra = 0, 16, 32, 48 more segments)."""
+    def around(edge):
+        return lambda x: (edge - (4 + x // 2) * SEG, edge + (4 + x // 2) * SEG)
+    return [
+        ("w0", [], None, lambda x: (SEG + 12345, (17 + x) * SEG + 12345)),
+        ("w1", [1, 2, 3, 4], None, lambda x: (SEG + 777, 33 * SEG - 4321)),
+        ("w2", 8, 8001, lambda x: (2 * SEG + 54321, (18 + x) * SEG + 54321)),
+        ("w3", 12, 12001, lambda x: (SEG + 999, (17 + x) * SEG + 999)),
+        ("m0", 64, 64001, lambda x: (SEG + 4097, (9 + x) * SEG + 4097)),
+        ("m3", 76, 76001, lambda x: (3 * SEG + 31, (11 + x) * SEG + 31)),
+        ("l56", [1, 2, 3, 4], None, around(1 << 40)),
+        ("l67", [1, 2, 3, 4], None, around(1 << 48)),
+        ("top", [1, 2, 3, 4], None, lambda x: (K_LIMIT - (8 + x) * SEG, K_LIMIT)),
+    ]
+
+
+def seg_inner(path):
+    import time
+    t_all = time.time()
+    with open(os.path.join(HERE, "pow_golden.json")) as f:
+        golden = json.load(f)
+    exe = build_fast_scan()
+    lib = load_oracle()
+    seg_inner_crosscheck(exe, lib, golden)
+    print(f"cross-checks: {time.time() - t_all:.0f} s", file=sys.stderr)
+
+    def scan(name, nonce, win, need):
+        """Lengthen in 16-segment steps until `need` holds; None when 64 segments do not do."""
+        hits, done_to = [], None
+        for extra in range(0, MAX_SEGS, 16):
+            k0, k1 = win(extra)
+            if (k1 - k0 + SEG - 1) // SEG > MAX_SEGS:
+                break
+            t = time.time()
+            if done_to is None:
+                hits = fast_scan_all(exe, nonce, SEG_INNER_NTZ, k0, k1)
+            elif (k0, k1) == done_to:
+                break  # a fixed window
+            else:  # only the new k: below and above what is scanned
+                hits = (fast_scan_all(exe, nonce, SEG_INNER_NTZ, k0, done_to[0]) + hits
+                        + fast_scan_all(exe, nonce, SEG_INNER_NTZ, done_to[1], k1))
+            done_to = (k0, k1)
+            print(f"{name}: [{k0}, {k1}) {len(hits)} entries, {sum(tz >= 9 for _, tz in hits)} with tz >= 9 "
+                  f"({time.time() - t:.0f} s)", file=sys.stderr)
+            if need(hits):
+                return {"name": name, "nonce": list(nonce), "k_begin": k0, "k_end": k1, "hits": hits}
+        return None
+
+    # the cases that are not their W0's first: >= 4 entries; then the first of each W0 also has to
+    # provide the N = 9 entry behind an N = 8 one if no other case of that W0 does
+    group = {"w0": ("m0",), "w1": ("l56", "l67", "top"), "w2": (), "w3": ("m3",)}
+    spec = {c[0]: c for c in seg_inner_cases()}
+    done = {}
+
+    def run(name, need):
+        _, nonce, seed, win = spec[name]
+        attempt = 0
+        while True:
+            nv = nonce if seed is None else seeded_nonce(seed + attempt, nonce)
+            c = scan(name, nv, win, need)
+            if c is not None:
+                done[name] = c
+                return
+            assert seed is not None, f"{name}: a fixed nonce misses its condition at {MAX_SEGS} segments"
+            attempt += 1
+
+    for first, others in group.items():
+        for name in others:
+            run(name, lambda h: len(h) >= 4)
+        covered = any(_n9_after_8(done[o]["hits"]) for o in others)
+        run(first, lambda h: len(h) >= 4 and (covered or _n9_after_8(h)))
+
+    cases = [done[c[0]] for c in seg_inner_cases()]
+    for c in cases:
+        gs = [g for g, _ in c["hits"]]
+        assert gs == sorted(set(gs)) and all(c["k_begin"] <= g >> 8 < c["k_end"] for g in gs), c["name"]
+        for g, tz in c["hits"]:
+            assert tz >= SEG_INNER_NTZ and tz_of(c["nonce"], g) == tz, (c["name"], g, tz)
+    first9 = next(g for g, tz in done["w1"]["hits"] if tz >= 9)
+    assert first9 == N9_GOLDEN and _n9_after_8(done["w1"]["hits"]), first9
+    with open(path, "w") as f:
+        json.dump({"ntz": SEG_INNER_NTZ, "cases": cases}, f, indent=0, separators=(",", ":"))
+        f.write("\n")
+    for c in cases:
+        print(f"{c['name']}: {len(c['hits'])} entries, {sum(tz >= 9 for _, tz in c['hits'])} with tz >= 9",
+              file=sys.stderr)
+    print(f"--seg-inner: {time.time() - t_all:.0f} s", file=sys.stderr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--big", action="store_true", help="also compute N=7/8 cases via the C oracle")
     ap.add_argument("--deep", action="store_true", help="add N=9/10 hits (fast_scan) to the existing file")
+    ap.add_argument("--seg-inner", action="store_true",
+                    help="write seg_inner_hits.json: all-hits lists for the segment-inner kernels (fast_scan)")
     args = ap.parse_args()
+    if args.seg_inner:
+        seg_inner(os.path.join(HERE, "seg_inner_hits.json"))
+        return
     if args.deep:
         deep(os.path.join(HERE, "pow_golden.json"))
         return
