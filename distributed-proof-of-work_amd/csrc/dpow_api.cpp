@@ -31,6 +31,7 @@
 
 #include "../../include/dpow.h"
 #include "../../include/dpow_worker.h"
+#include "batch.h"
 #include "dpow_common.h"
 #include "md5_host.h"
 #include "md5_variants.h"
@@ -258,6 +259,7 @@ struct dpow_ctx {
     uint64_t dev_key = 0;  // the GPU's identity across processes: a hash of its PCI bus id (dpow::device_key)
     std::atomic<int64_t> last_use{0};  // now_ns() of dpow_open / the last search start (recent_contexts)
     bool solo = false;  // dpow_board_search's node-wide role: no young-search sharing (plan.h kYoungNs)
+    BatchState *batch = nullptr;  // buffers of dpow_search_batch: allocated by the first batch (batch.cpp)
 };
 
 namespace {
@@ -882,6 +884,7 @@ void dpow_close(dpow_ctx *c) {
     // before the stream is destroyed (dpow_node_release synchronizes every holder's stream).
     c->node = c->d_node = nullptr;
     pages_release_ctx(c);
+    batch_free(c->batch);
     if (c->d_ctrl_alloc) (void)hipFree(c->d_ctrl_alloc);
     if (c->d_claims) (void)hipFree(c->d_claims);
     if (c->h_snap) (void)hipHostFree(c->h_snap);
@@ -1597,6 +1600,17 @@ int dpow_diag_dword_test(const uint8_t *nonce, size_t nonce_len, uint32_t ntz, u
     const uint32_t D = iv_d + state_d;
     const bool pre = use_d_equality(nblk, ntz) ? state_d == L.deq : D <= L.dle;
     return pre && (D & L.dmask) == 0u ? 1 : 0;
+}
+
+int dpow_search_batch(dpow_ctx *c, dpow_batch_task *tasks, size_t n_tasks, dpow_batch_stats *stats) {
+    const int rc = batch_check(tasks, n_tasks);  // the tasks' own errors first: they need no context
+    if (rc < 0) return rc;
+    if (!c) return set_error(DPOW_EINVAL, "dpow_search_batch: ctx is NULL");
+    if (c->node) return set_error(DPOW_EINVAL, "dpow_search_batch: a node slot is attached to the context");
+    const DeviceScope on_device(c->device);
+    if (on_device.e != hipSuccess) return hip_fail(on_device.e, "hipSetDevice");
+    c->last_use.store(now_ns(), std::memory_order_relaxed);
+    return batch_run(&c->batch, c->stream, c->h_cancel, tasks, n_tasks, stats);
 }
 
 int dpow_search(dpow_ctx *c, const uint8_t *nonce, size_t nonce_len, uint32_t ntz, uint32_t worker_byte,

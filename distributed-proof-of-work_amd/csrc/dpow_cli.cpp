@@ -9,7 +9,10 @@
 //       latency for hits at N = 0 / 3 / 5 (in-process, warm context)
 //   dpow_cli worker <nonce-hex> <ntz> [device]
 //       one Mine -> result -> Found -> ACK round trip through the native worker (worker.go:169-232)
-// Each command prints one JSON line.
+//   dpow_cli batch <ntz> <nonce-hex> [<nonce-hex> ...] [--device N]
+//       mine every nonce from k = 0 in one batched search (dpow_search_batch), window by window;
+//       one line per task: its global index and its secret in hex
+// Each other command prints one JSON line.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -179,7 +182,63 @@ static int cmd_worker(int argc, char **argv) {
     return 0;
 }
 
+static int cmd_batch(int argc, char **argv) {
+    if (argc < 4) return 2;
+    const uint32_t ntz = (uint32_t)atoi(argv[2]);
+    int dev = 0;
+    std::vector<std::vector<uint8_t>> nonces;
+    for (int i = 3; i < argc; ++i) {
+        if (!strcmp(argv[i], "--device") && i + 1 < argc) dev = atoi(argv[++i]);
+        else nonces.push_back(from_hex(argv[i]));
+    }
+    if (nonces.empty() || nonces.size() > DPOW_BATCH_MAX) return 2;
+    dpow_ctx *ctx = nullptr;
+    int rc = dpow_open(dev, &ctx);
+    if (rc) return fail("dpow_open", rc);
+    const size_t n = nonces.size();
+    std::vector<dpow_batch_task> done(n);
+    std::vector<size_t> todo(n);
+    for (size_t i = 0; i < n; ++i) todo[i] = i;
+    uint64_t k = 0, window = 1ull << 20;
+    while (!todo.empty() && k < DPOW_K_LIMIT) {
+        const uint64_t ke = k + window < DPOW_K_LIMIT ? k + window : DPOW_K_LIMIT;
+        std::vector<dpow_batch_task> tasks(todo.size());
+        for (size_t j = 0; j < todo.size(); ++j) {
+            dpow_batch_task &t = tasks[j];
+            memset(&t, 0, sizeof t);
+            t.nonce = nonces[todo[j]].data();
+            t.nonce_len = nonces[todo[j]].size();
+            t.ntz = ntz;
+            t.k_begin = k;
+            t.k_end = ke;
+            t.best_global_idx = DPOW_NO_HIT;
+        }
+        rc = dpow_search_batch(ctx, tasks.data(), tasks.size(), nullptr);
+        if (rc < 0) return fail("dpow_search_batch", rc);
+        std::vector<size_t> left;
+        for (size_t j = 0; j < todo.size(); ++j) {
+            done[todo[j]] = tasks[j];
+            if (tasks[j].status == DPOW_EXHAUSTED) left.push_back(todo[j]);
+        }
+        todo.swap(left);
+        k = ke;
+        if (window < (1ull << 26)) window <<= 2;
+    }
+    for (size_t i = 0; i < n; ++i) {
+        if (done[i].status != DPOW_FOUND) {
+            printf("%zu status %d\n", i, done[i].status);
+            continue;
+        }
+        printf("%zu %llu ", i, (unsigned long long)done[i].best_global_idx);
+        for (uint32_t b = 0; b < done[i].secret_len; ++b) printf("%02x", done[i].secret[b]);
+        printf("\n");
+    }
+    dpow_close(ctx);
+    return 0;
+}
+
 int main(int argc, char **argv) {
+    if (argc >= 2 && !strcmp(argv[1], "batch")) return cmd_batch(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "mine")) return cmd_mine(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "sweep")) return cmd_sweep(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "worker")) return cmd_worker(argc, argv);
@@ -188,6 +247,7 @@ int main(int argc, char **argv) {
             "usage: dpow_cli mine <nonce-hex> <ntz> [worker_byte worker_bits [device]]\n"
             "       dpow_cli sweep <log2-candidates> [device]\n"
             "       dpow_cli worker <nonce-hex> <ntz> [device]\n"
-            "       dpow_cli latency [reps [device]]\n");
+            "       dpow_cli latency [reps [device]]\n"
+            "       dpow_cli batch <ntz> <nonce-hex> [<nonce-hex> ...] [--device N]\n");
     return 2;
 }

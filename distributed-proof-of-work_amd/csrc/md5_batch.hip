@@ -1,0 +1,156 @@
+// md5_batch.hip -- the generic kernel of the batched search (dpow_search_batch, batch.cpp).
+//
+// One launch hashes a slice of every live task's window.  Workgroup b takes row b / n_live of
+// live entry b % n_live (chunk-major: a task's early indices are dispatched first), one candidate
+// per lane and 256 per step, in increasing index order.  The task's fields are wave-uniform and
+// come from the task table with scalar loads; the message layout is data (md5_batch.h
+// batch_candidate_words), so k = 0, every chunk-length boundary and both block counts go through
+// the same code; a workgroup branches once on its task's wave-uniform p / 4, so that the word
+// positions of the variable bytes are compile-time constants inside the hash.  A wave hashes the
+// second final block when any of its lanes needs it.
+//
+// Exactness: a hit goes to the task's best with atomicMin on the global index, which is monotone
+// in the local index.  A workgroup stops at the first step whose lowest global index is at or
+// above the task's current best; best only ever holds the task's bound or a hit, so no candidate
+// below the final best is skipped.
+//
+// No wave waits for another wave or for the host: the grid is bounded, a workgroup's work is
+// fixed at its start, and the only cross-workgroup state is the retirement count whose last
+// increment copies the live tasks' best values and the completion record to pinned memory.
+#include <hip/hip_runtime.h>
+
+#include "md5_batch.h"
+
+namespace dpow {
+
+namespace {
+
+// One workgroup's range [lo, hi) of one task, with p / 4 a compile-time constant (md5_batch.h
+// batch_with_w0): 256 candidates per step, one per lane, in increasing index order.
+struct BatchGroup {
+    const BatchTask *t;
+    unsigned long long *bp;  // the task's best
+    uint64_t lo, hi;
+
+    template <int W0>
+    __device__ __forceinline__ void operator()() const {
+        const uint32_t p = t->p, rbits = t->rbits, base_tb = t->base_tb, ntz = t->ntz, len_bits = t->len_bits;
+        const uint32_t dmask = t->dmask;
+        // the template and the midstate, loaded once per workgroup (wave-uniform: SGPRs)
+        uint32_t T[16], iv[4];
+#pragma unroll
+        for (int w = 0; w < 16; ++w) T[w] = t->T[w];
+#pragma unroll
+        for (int w = 0; w < 4; ++w) iv[w] = t->iv[w];
+        const uint32_t lane = threadIdx.x & 63u;
+        // The task's best is read one step ahead (the load is in flight while the step hashes); a
+        // value one step old only delays the early exit, it skips nothing.
+        unsigned long long best = __hip_atomic_load(bp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        for (uint64_t i0 = lo + (threadIdx.x & ~63u); i0 < hi; i0 += kBlockThreads) {  // i0: the wave's first index
+            if (global_of_local(i0, rbits, base_tb) >= best) break;
+            best = __hip_atomic_load(bp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            uint64_t i = i0 + lane;
+            const bool act = i < hi;
+            if (!act) i = hi - 1;
+            uint32_t M[32];
+            const uint32_t nblk = batch_candidate_words_at<W0>(T, p, rbits, base_tb, len_bits, i, M);
+            uint32_t st[4] = {iv[0], iv[1], iv[2], iv[3]};
+            batch_md5_block(st, M);
+            if constexpr (W0 > 11) {  // p + 1 + L > 55 needs p >= 48
+                if (__any(nblk == 2u)) {
+                    uint32_t s2[4] = {st[0], st[1], st[2], st[3]};
+                    batch_md5_block(s2, M + 16);
+#pragma unroll
+                    for (int w = 0; w < 4; ++w) st[w] = nblk == 2u ? s2[w] : st[w];
+                }
+            }
+            const bool cand = act && (st[3] & dmask) == 0u;
+            if (__ballot(cand) != 0ull) {
+                const bool ok = cand && trailing_zero_nibbles(st[0], st[1], st[2], st[3]) >= ntz;
+                const unsigned long long m = __ballot(ok);
+                if (m != 0ull && lane == (uint32_t)(__ffsll((long long)m) - 1)) {
+                    // The returned value is consumed, so the wave waits for the atomic: it is
+                    // performed before the workgroup's retirement count (below).
+                    const unsigned long long prev = __hip_atomic_fetch_min(
+                        bp, (unsigned long long)global_of_local(i, rbits, base_tb), __ATOMIC_RELAXED,
+                        __HIP_MEMORY_SCOPE_AGENT);
+                    asm volatile("; dpow batch: atomicMin performed (%0)" ::"v"(prev));
+                }
+            }
+        }
+    }
+};
+
+__global__ void __launch_bounds__(kBlockThreads)
+    batch_kernel(const BatchTask *__restrict__ tasks, const BatchEntry *__restrict__ map, const BatchLaunch L) {
+    __shared__ uint32_t s_last;
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        __hip_atomic_store(L.t0, __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint32_t row = blockIdx.x / L.n_live;
+    const uint32_t j = blockIdx.x - row * L.n_live;
+    const BatchEntry *const e = map + j;
+    uint64_t lo, hi;
+    if (batch_block_range(e->i_begin, e->i_end, row, L.group, lo, hi)) {
+        const uint32_t ti = e->task;
+        const BatchGroup g{tasks + ti, L.best + ti, lo, hi};
+        batch_with_w0(__builtin_amdgcn_readfirstlane(g.t->p >> 2), g);
+    }
+    // Retirement, counted per workgroup.  Each wave's atomicMin has been performed already (the
+    // hit path consumes the returning atomic's result), the barrier covers the four waves, so the
+    // count comes after every hit of the workgroup.  (An agent-scope release fence here instead
+    // cost every wave an L2 write-back: ~0.2 ms per launch of 4096 small workgroups.)  The
+    // workgroup whose count completes the launch copies the live tasks' best values out and
+    // writes the completion record, from one wave.
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint32_t prev = __hip_atomic_fetch_add(L.done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        s_last = prev + 1u == L.n_blocks ? 1u : 0u;
+    }
+    __syncthreads();
+    if (s_last != 0u && threadIdx.x < 64u) {
+        for (uint32_t q = threadIdx.x; q < L.n_live; q += 64u) {
+            const unsigned long long b =
+                __hip_atomic_load(L.best + map[q].task, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(L.out_best + q, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");  // the wave's stores before its lane 0's record
+        if (threadIdx.x == 0) {
+            __hip_atomic_store(L.done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const unsigned long long t_start = __hip_atomic_load(L.t0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&L.rec->t_start, t_start, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(&L.rec->t_end, __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(&L.rec->seq, L.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+}
+
+// The upload image, pinned host memory to device memory (batch_upload).
+__global__ void __launch_bounds__(kBlockThreads)
+    batch_upload_kernel(uint32_t *__restrict__ dst, const uint32_t *__restrict__ src, uint32_t n_words) {
+    for (uint32_t w = blockIdx.x * blockDim.x + threadIdx.x; w < n_words; w += gridDim.x * blockDim.x) dst[w] = src[w];
+}
+
+}  // namespace
+
+hipError_t batch_prepare() {
+    hipFuncAttributes a;
+    hipError_t e = hipFuncGetAttributes(&a, reinterpret_cast<const void *>(batch_kernel));
+    if (e == hipSuccess) e = hipFuncGetAttributes(&a, reinterpret_cast<const void *>(batch_upload_kernel));
+    return e;
+}
+
+hipError_t batch_upload(uint32_t *dst, const uint32_t *src, uint32_t n_words, hipStream_t stream) {
+    const uint32_t blocks = (n_words + 4u * kBlockThreads - 1u) / (4u * kBlockThreads);
+    hipLaunchKernelGGL(batch_upload_kernel, dim3(blocks ? blocks : 1u), dim3(kBlockThreads), 0, stream, dst, src,
+                       n_words);
+    return hipGetLastError();
+}
+
+hipError_t batch_launch(const BatchTask *tasks, const BatchEntry *map, const BatchLaunch &L, hipStream_t stream) {
+    hipLaunchKernelGGL(batch_kernel, dim3(L.n_blocks), dim3(kBlockThreads), 0, stream, tasks, map, L);
+    return hipGetLastError();
+}
+
+}  // namespace dpow

@@ -68,6 +68,30 @@ class Stats(ctypes.Structure):
                 ("candidates", ctypes.c_uint64), ("kernel_ms", ctypes.c_double)]
 
 
+DPOW_BATCH_MAX = 4096
+
+
+class BatchTaskC(ctypes.Structure):
+    """dpow_batch_task (include/dpow.h)."""
+    _fields_ = [("nonce", ctypes.c_void_p), ("nonce_len", ctypes.c_size_t),
+                ("ntz", ctypes.c_uint32), ("worker_byte", ctypes.c_uint32), ("worker_bits", ctypes.c_uint32),
+                ("k_begin", ctypes.c_uint64), ("k_end", ctypes.c_uint64), ("best_global_idx", ctypes.c_uint64),
+                ("status", ctypes.c_int32), ("secret_len", ctypes.c_uint32),
+                ("secret", ctypes.c_uint8 * DPOW_MAX_SECRET)]
+
+
+class BatchStats(ctypes.Structure):
+    """dpow_batch_stats (include/dpow.h)."""
+    _fields_ = [("launches", ctypes.c_uint32), ("rounds", ctypes.c_uint32), ("candidates", ctypes.c_uint64),
+                ("kernel_ms", ctypes.c_double)]
+
+
+class BatchRange(ctypes.Structure):
+    """dpow_batch_range (include/dpow.h)."""
+    _fields_ = [("launch", ctypes.c_uint32), ("task", ctypes.c_uint32), ("i_begin", ctypes.c_uint64),
+                ("i_end", ctypes.c_uint64), ("group", ctypes.c_uint32), ("rows", ctypes.c_uint32)]
+
+
 _lib = None
 
 
@@ -225,6 +249,14 @@ def lib():
                                             ctypes.c_size_t]),
         "dpow_plan_candidate": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32,
                                                ctypes.c_uint64, u32p, u32p, u32p]),
+        "dpow_search_batch": (ctypes.c_int, [vp, ctypes.POINTER(BatchTaskC), ctypes.c_size_t,
+                                             ctypes.POINTER(BatchStats)]),
+        "dpow_batch_candidate": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32,
+                                                ctypes.c_uint64, u32p, u32p, u32p]),
+        "dpow_batch_plan": (ctypes.c_int, [u64p, u64p, u32p, ctypes.c_size_t, ctypes.POINTER(BatchRange),
+                                           ctypes.c_size_t, u64p]),
+        "dpow_batch_plan_block": (ctypes.c_int, [ctypes.POINTER(BatchRange), ctypes.c_uint32, ctypes.c_uint32,
+                                                 u32p, u64p, u64p]),
         "dpow_get_stats": (ctypes.c_int, [vp, ctypes.POINTER(Stats)]),
         "dpow_reset_stats": (None, [vp]),
         "dpow_stream": (vp, [vp]),

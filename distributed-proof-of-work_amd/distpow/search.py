@@ -14,7 +14,8 @@ from . import _lib
 from ._lib import (CANCELLED, DPOW_K_LIMIT, DPOW_MAX_SECRET, DPOW_NO_HIT, EXHAUSTED, FOUND, DpowError,
                    PlanLaunch, Stats, check, lib)
 
-__all__ = ["Miner", "SearchResult", "secret_from_index", "md5", "verify", "trailing_zero_nibbles",
+__all__ = ["Miner", "SearchResult", "BatchTask", "batch_candidate", "batch_plan", "batch_plan_block",
+           "secret_from_index", "md5", "verify", "trailing_zero_nibbles",
            "thread_bytes", "remainder_bits", "global_index", "plan_window", "plan_candidate",
            "device_count", "DPOW_NO_HIT", "FOUND", "EXHAUSTED", "CANCELLED"]
 
@@ -93,6 +94,53 @@ def plan_candidate(nonce, worker_byte, worker_bits, local_idx):
     check(lib().dpow_plan_candidate(n, len(n), worker_byte, worker_bits, local_idx, iv, words,
                                     ctypes.byref(nblk)), "dpow_plan_candidate")
     return list(iv), list(words[:16 * nblk.value]), nblk.value
+
+
+@dataclass
+class BatchTask:
+    """One task of Miner.search_batch: the arguments of Miner.search (dpow_batch_task)."""
+    nonce: Sequence[int]
+    num_trailing_zeros: int
+    worker_byte: int = 0
+    worker_bits: int = 0
+    k_begin: int = 0
+    k_end: int = 1
+    bound: int = DPOW_NO_HIT
+
+
+def batch_candidate(nonce, worker_byte, worker_bits, local_idx):
+    """(iv[4], words[16*nblk], nblk) the batch kernel hashes for one candidate (dpow_batch_candidate)."""
+    n = _b(nonce)
+    iv = (ctypes.c_uint32 * 4)()
+    words = (ctypes.c_uint32 * 32)()
+    nblk = ctypes.c_uint32()
+    check(lib().dpow_batch_candidate(n, len(n), worker_byte, worker_bits, local_idx, iv, words,
+                                     ctypes.byref(nblk)), "dpow_batch_candidate")
+    return list(iv), list(words[:16 * nblk.value]), nblk.value
+
+
+def batch_plan(windows):
+    """The launches dpow_search_batch queues for windows [(k_begin, k_end, worker_bits), ...] when no
+    task hits (dpow_batch_plan): (entries, launches), entries a ctypes array of BatchRange, one per
+    (launch, live task) in block-map order."""
+    n = len(windows)
+    kb = (ctypes.c_uint64 * max(n, 1))(*[w[0] for w in windows])
+    ke = (ctypes.c_uint64 * max(n, 1))(*[w[1] for w in windows])
+    wb = (ctypes.c_uint32 * max(n, 1))(*[w[2] for w in windows])
+    launches = ctypes.c_uint64()
+    cnt = check(lib().dpow_batch_plan(kb, ke, wb, n, None, 0, ctypes.byref(launches)), "dpow_batch_plan")
+    arr = (_lib.BatchRange * max(cnt, 1))()
+    check(lib().dpow_batch_plan(kb, ke, wb, n, arr, cnt, ctypes.byref(launches)), "dpow_batch_plan")
+    return (_lib.BatchRange * cnt).from_buffer(arr), launches.value
+
+
+def batch_plan_block(entries, n_live, block):
+    """(task, lo, hi) of workgroup `block` of a launch whose n_live entries start at entries[0], or
+    None when the workgroup has nothing to hash (dpow_batch_plan_block: the kernel's block map)."""
+    task, lo, hi = ctypes.c_uint32(), ctypes.c_uint64(), ctypes.c_uint64()
+    r = check(lib().dpow_batch_plan_block(entries, n_live, block, ctypes.byref(task), ctypes.byref(lo),
+                                          ctypes.byref(hi)), "dpow_batch_plan_block")
+    return (task.value, lo.value, hi.value) if r else None
 
 
 def device_count() -> int:
@@ -180,6 +228,53 @@ class Miner:
                 return res
             k = ke
         return SearchResult(EXHAUSTED)
+
+    # -- batched search ---------------------------------------------------------
+    def search_batch(self, tasks: Sequence[BatchTask]) -> List[SearchResult]:
+        """B independent windows in one pass over the GPU (dpow_search_batch): result i is what
+        `search` returns for tasks[i].  The call's launch counts are kept in last_batch_stats."""
+        n = len(tasks)
+        arr = (_lib.BatchTaskC * max(n, 1))()
+        nonces = [_b(t.nonce) for t in tasks]
+        buf = ctypes.create_string_buffer(b"".join(nonces), max(sum(map(len, nonces)), 1))  # alive for the call
+        addr = ctypes.addressof(buf)
+        for t, nb, c in zip(tasks, nonces, arr):
+            c.nonce, c.nonce_len = addr, len(nb)
+            addr += len(nb)
+            c.ntz, c.worker_byte, c.worker_bits = t.num_trailing_zeros, t.worker_byte, t.worker_bits
+            c.k_begin, c.k_end, c.best_global_idx = t.k_begin, t.k_end, t.bound
+        st = _lib.BatchStats()
+        check(lib().dpow_search_batch(self._ctx, arr, n, ctypes.byref(st)), "dpow_search_batch")
+        self.last_batch_stats = st
+        return [SearchResult(FOUND, c.best_global_idx, bytes(c.secret[:c.secret_len])) if c.status == FOUND
+                else SearchResult(c.status) for c in arr[:n]]
+
+    def mine_many(self, requests: Sequence[BatchTask], k_limit: int = DPOW_K_LIMIT,
+                  window: int = DEFAULT_WINDOW) -> List[SearchResult]:
+        """`mine` for many requests at once: every unfinished request advances window by window
+        from its k_begin (its k_end is ignored) through search_batch, until each has a hit, the
+        cancel flag is raised, or k_limit is reached."""
+        out: List[Optional[SearchResult]] = [None] * len(requests)
+        k = [r.k_begin for r in requests]
+        todo = [i for i in range(len(requests))]
+        while todo:
+            for i in [i for i in todo if k[i] >= k_limit]:
+                out[i] = SearchResult(EXHAUSTED)
+            todo = [i for i in todo if out[i] is None]
+            if not todo:
+                break
+            batch = [BatchTask(requests[i].nonce, requests[i].num_trailing_zeros, requests[i].worker_byte,
+                               requests[i].worker_bits, k[i], min(k_limit, k[i] + window), requests[i].bound)
+                     for i in todo]
+            results = []
+            for off in range(0, len(batch), _lib.DPOW_BATCH_MAX):  # at most DPOW_BATCH_MAX tasks per call
+                results += self.search_batch(batch[off:off + _lib.DPOW_BATCH_MAX])
+            for i, t, res in zip(todo, batch, results):
+                if res.status != EXHAUSTED:
+                    out[i] = res
+                k[i] = t.k_end
+            todo = [i for i in todo if out[i] is None]
+        return out
 
     # -- measurement ------------------------------------------------------------
     def stats(self) -> Stats:

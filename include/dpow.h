@@ -31,6 +31,9 @@ extern "C" {
  * 3 (round 4): dpow_diag_launch_geometry takes ntz (dpow_diag.h); dpow_node_release.
  * 4 (round 5): dpow_node_mine.
  * 5 (round 6): the node board, dpow_board_* (the node scheduler under the coordinator protocol).
+ * The batch entry points (dpow_search_batch, dpow_batch_candidate, dpow_batch_plan,
+ * dpow_batch_plan_block) were added within ABI 5: nothing older changed, and the Python binding
+ * refuses a library that lacks a prototype it lists, or one built from another tree.
  * A consumer built against another version must refuse the library before any
  * other call (distpow/_lib.py check_abi, tests/c/abi_harness.c). */
 #define DPOW_ABI_VERSION 5
@@ -111,6 +114,50 @@ int dpow_search(dpow_ctx *ctx, const uint8_t *nonce, size_t nonce_len, uint32_t 
  * coordinator.go:210-230, cancels instead).  No effect when no search runs.
  * Returns 0 or a negative error code. */
 int dpow_search_bound(dpow_ctx *ctx, uint64_t global_idx);
+
+/* ---------------------------------------------------------------------------
+ * Batched search (added within ABI 5): B independent tasks in one pass over the GPU.
+ *
+ * The reference coordinator takes any number of concurrent Mine requests
+ * (coordinator.go:139-199); a caller holding B small tasks (a node scheduler, a
+ * worker, a benchmarking client) pays the launch and completion round trip once
+ * per round here instead of once per task.  Each task is a dpow_search argument
+ * tuple and gets the answer dpow_search gives for it on an idle context: the first
+ * hit below its bound in the reference's order (worker.go:318-400), re-verified
+ * with the host MD5 before DPOW_FOUND is written.  Tasks are independent (a task's
+ * result does not depend on the others of its batch; duplicates are legal).
+ *
+ * One generic kernel (csrc/md5_batch.hip) hashes the tasks in rounds: round r
+ * covers the next slice of every undecided task's window, slices growing 4x per
+ * round up to a cap of a few milliseconds of hashing.
+ *
+ * Returns 0, or a negative code with no task written: DPOW_EINVAL for a NULL
+ * pointer, n_tasks of 0 or above DPOW_BATCH_MAX, k_begin > k_end, worker_byte >
+ * 255, a nonce longer than DPOW_MAX_NONCE (dpow_worker.h) or a context with a
+ * node slot attached; DPOW_ERANGE for k_end > DPOW_K_LIMIT; all of these before any
+ * GPU work.  The context's cancel flag ends the call: undecided tasks get
+ * DPOW_CANCELLED, decided ones keep their answer; a flag raised on entry cancels
+ * every task without a launch.  dpow_search_bound has no effect on a batch, and a
+ * batch does not touch dpow_stats: its counts go to *stats.  One batch or search
+ * is in flight per context.
+ * ------------------------------------------------------------------------- */
+#define DPOW_BATCH_MAX 4096
+typedef struct dpow_batch_task {
+    const uint8_t *nonce;         /* in */
+    size_t nonce_len;             /* in */
+    uint32_t ntz, worker_byte, worker_bits;  /* in */
+    uint64_t k_begin, k_end;      /* in */
+    uint64_t best_global_idx;     /* in: bound (DPOW_NO_HIT = none); out: the hit */
+    int32_t status;               /* out: DPOW_FOUND / DPOW_EXHAUSTED / DPOW_CANCELLED */
+    uint32_t secret_len;          /* out on DPOW_FOUND */
+    uint8_t secret[DPOW_MAX_SECRET];
+} dpow_batch_task;
+typedef struct dpow_batch_stats {
+    uint32_t launches, rounds;    /* kernel launches; rounds of the schedule (one launch each) */
+    uint64_t candidates;          /* candidates covered by the launches' slices */
+    double kernel_ms;             /* sum of the launches' durations, as they stamp them */
+} dpow_batch_stats;
+int dpow_search_batch(dpow_ctx *ctx, dpow_batch_task *tasks, size_t n_tasks, dpow_batch_stats *stats);
 
 /* ---------------------------------------------------------------------------
  * Node slot (round 3): the Found fan-out of one node's ranks, in shared memory.
@@ -296,6 +343,36 @@ int dpow_plan_window(const uint8_t *nonce, size_t nonce_len, uint32_t ntz, uint3
 int dpow_plan_candidate(const uint8_t *nonce, size_t nonce_len, uint32_t worker_byte,
                         uint32_t worker_bits, uint64_t local_idx, uint32_t iv_out[4],
                         uint32_t words_out[32], uint32_t *nblk_out);
+
+/* Final-block words and chaining value the batch kernel hashes for local index `local_idx`
+ * of a partition, assembled by the code the kernel itself calls (csrc/md5_batch.h
+ * batch_candidate_words).  words_out: 16 * (*nblk_out) words (the rest zero). */
+int dpow_batch_candidate(const uint8_t *nonce, size_t nonce_len, uint32_t worker_byte,
+                         uint32_t worker_bits, uint64_t local_idx, uint32_t iv_out[4],
+                         uint32_t words_out[32], uint32_t *nblk_out);
+
+/* Round plan of a batch (host logic of dpow_search_batch, exposed for testing): the
+ * launches the host loop queues for tasks with windows [k_begin[i], k_end[i]) and
+ * partitions worker_bits[i] when no task hits.  One entry per (launch, live task), in
+ * launch order and, within a launch, in the order of the launch's block map: the
+ * slice [i_begin, i_end) of the task's local indices (k * R + t) the launch covers,
+ * cut into `rows` workgroup groups of `group` local indices.  Workgroup b of a launch
+ * with n live entries hashes row b / n of entry b % n (dpow_batch_plan_block).
+ * Returns the number of entries (may exceed max_entries, in which case only the first
+ * max_entries are written) or a negative error code; *launches_out = launches. */
+typedef struct dpow_batch_range {
+    uint32_t launch, task;     /* launch number (= round), task index */
+    uint64_t i_begin, i_end;   /* local index slice of this launch */
+    uint32_t group, rows;      /* the launch's workgroup size in local indices, rows per entry */
+} dpow_batch_range;
+int dpow_batch_plan(const uint64_t *k_begin, const uint64_t *k_end, const uint32_t *worker_bits,
+                    size_t n_tasks, dpow_batch_range *out, size_t max_entries, uint64_t *launches_out);
+/* The local index range workgroup `block` of a launch hashes, by the kernel's own block
+ * map arithmetic: entries = the launch's n_live entries of dpow_batch_plan.  Returns 1
+ * with *task, *lo, *hi, 0 when the workgroup has nothing to hash (its entry's slice ended
+ * in an earlier row), or a negative error code. */
+int dpow_batch_plan_block(const dpow_batch_range *entries, uint32_t n_live, uint32_t block,
+                          uint32_t *task, uint64_t *lo, uint64_t *hi);
 
 /* ---------------------------------------------------------------------------
  * Introspection / measurement.

@@ -25,6 +25,8 @@
 #   small <cases|random|stop> [knobs]   short-search launch knobs (tools/small_search_probe.py)
 #   ab lib.so ...    sweep-rate A/B of prebuilt libraries (tools/ab_variants.py)
 #   node-ab runs name=lib.so[,VAR=value...] ...   the emulated 8-GPU node per library, then ab
+#   batch [reps]     the batched search's GPU tests, then its tasks-per-second table against the looped
+#                    and the 8-thread paths (tools/batch_rate.py -> batch_rate.json)
 set -o pipefail
 task=${1:?task}; tag=${2:?tag}; shift 2
 out=gpurun_out/$tag
@@ -101,6 +103,10 @@ small)
     mode=${1:-cases}; shift
     flag=""; [ "$mode" != cases ] && flag="--$mode"
     timeout -k 10 500 python3 -u tools/small_search_probe.py $flag "$@" > $out/$mode.json 2> $out/$mode.err ;;
+batch)
+    timeout -k 10 300 python3 -u -m pytest tests/test_gpu_batch.py -m gpu -x -v -s > $out/pytest_batch.txt 2>&1 &&
+    timeout -k 10 500 python3 -u tools/batch_rate.py --reps "${1:-5}" --out $out/batch_rate.json \
+        > $out/batch_rate.txt 2> $out/batch_rate.err ;;
 ab) timeout -k 10 800 python3 -u tools/ab_variants.py "$@" > $out/ab.log 2>&1 ;;
 node-ab)
     runs=$1; shift
