@@ -20,8 +20,16 @@
  * Nonces of 64 bytes and more: the whole nonce-only blocks are hashed by plain
  * scalar code (md5_block) into a midstate; the vectorised final block starts
  * from it, holds the nonce's last nonce_len mod 64 bytes and carries the bit
- * length of the whole message.  One final block must do:
- * nonce_len mod 64 + 1 + chunk length + 9 <= 64.
+ * length of the whole message.
+ *
+ * Two final blocks: with p = nonce_len mod 64, a message whose p + 1 + chunk
+ * length + 9 exceeds 64 pads into a second block (RFC 1321 3.1-3.2), and the
+ * chunk bytes, the 0x80 and the bit length fall wherever the byte count puts
+ * them.  The padded 128 bytes are laid out per k as plain bytes; the first
+ * block (which always holds the thread byte, p <= 63) runs vectorised from the
+ * midstate and the second, lane-uniform in its words, from each lane's state.
+ * gen_golden.py --layouts cross-checks this against the byte-wise oracle's
+ * all-hits lists and every two-block golden before it writes a list.
  *
  * All-hits mode (a sixth argument "all"): no best-so-far pruning; every
  * candidate of the window whose digest ends in >= ntz '0' characters is
@@ -163,9 +171,36 @@ static int cmp_hit(const void *a, const void *b) {
         }                                                                                  \
     } while (0)
 
+/* The 64 steps of one block on NV vectors of 16 lanes: st (A, B, C, D per lane) becomes
+ * st + rounds(st, mv), RFC 1321's chaining. */
+static inline __attribute__((always_inline)) void block_vec(__m512i st[4][NV], __m512i mv[16][NV]) {
+    __m512i a[NV], b[NV], c[NV], d[NV];
+    for (int v = 0; v < NV; ++v) a[v] = st[0][v], b[v] = st[1][v], c[v] = st[2][v], d[v] = st[3][v];
+#define R4(tt, r, i0, w0, w1, w2, w3)                       \
+    STEP(a, b, c, d, tt, mv[w0], i0 + 0, S[r][0]);          \
+    STEP(d, a, b, c, tt, mv[w1], i0 + 1, S[r][1]);          \
+    STEP(c, d, a, b, tt, mv[w2], i0 + 2, S[r][2]);          \
+    STEP(b, c, d, a, tt, mv[w3], i0 + 3, S[r][3]);
+    R4(TF, 0, 0, 0, 1, 2, 3) R4(TF, 0, 4, 4, 5, 6, 7) R4(TF, 0, 8, 8, 9, 10, 11)
+    R4(TF, 0, 12, 12, 13, 14, 15)
+    R4(TG, 1, 16, 1, 6, 11, 0) R4(TG, 1, 20, 5, 10, 15, 4) R4(TG, 1, 24, 9, 14, 3, 8)
+    R4(TG, 1, 28, 13, 2, 7, 12)
+    R4(TH, 2, 32, 5, 8, 11, 14) R4(TH, 2, 36, 1, 4, 7, 10) R4(TH, 2, 40, 13, 0, 3, 6)
+    R4(TH, 2, 44, 9, 12, 15, 2)
+    R4(TI, 3, 48, 0, 7, 14, 5) R4(TI, 3, 52, 12, 3, 10, 1) R4(TI, 3, 56, 8, 15, 6, 13)
+    R4(TI, 3, 60, 4, 11, 2, 9)
+#undef R4
+    for (int v = 0; v < NV; ++v) {
+        st[0][v] = _mm512_add_epi32(st[0][v], a[v]);
+        st[1][v] = _mm512_add_epi32(st[1][v], b[v]);
+        st[2][v] = _mm512_add_epi32(st[2][v], c[v]);
+        st[3][v] = _mm512_add_epi32(st[3][v], d[v]);
+    }
+}
+
 static void *scan_worker(void *arg) {
     job_t *j = (job_t *)arg;
-    const size_t p = j->nonce_len % 64; /* byte offset of the thread byte in the final block */
+    const size_t p = j->nonce_len % 64; /* byte offset of the thread byte in the first final block */
     const uint8_t *tail = j->nonce + (j->nonce_len - p);
     const __m512i lane = _mm512_set_epi32(15, 14, 13, 12, 11, 10, 9, 8, 7, 6, 5, 4, 3, 2, 1, 0);
     for (;;) {
@@ -174,54 +209,42 @@ static void *scan_worker(void *arg) {
         if (k0 >= j->k_end || (!j->all && k0 * 256u >= load_best(j))) return NULL;
         const uint64_t k1 = k0 + j->unit < j->k_end ? k0 + j->unit : j->k_end;
         for (uint64_t k = k0; k < k1; ++k) {
-            uint8_t buf[64];
+            /* The padded message behind the midstate (RFC 1321 3.1-3.2): the nonce's tail, the
+             * thread byte (left 0 here), the chunk, 0x80, zeroes, the bit length in the last 8
+             * bytes of the first 64-byte block with room for them: one block, or two. */
+            uint8_t buf[128];
             memset(buf, 0, sizeof buf);
             memcpy(buf, tail, p);
             size_t clen = 0;
             for (uint64_t x = k; x; x >>= 8) buf[p + 1 + clen++] = (uint8_t)(x & 0xFF);
             const size_t len = p + 1 + clen;
             buf[len] = 0x80;
+            const int nb = len + 9 > 64 ? 2 : 1;
             const uint64_t bits = (uint64_t)(j->nonce_len - p + len) * 8u;
-            for (int b = 0; b < 8; ++b) buf[56 + b] = (uint8_t)(bits >> (8 * b));
-            uint32_t M[16];
-            for (int w = 0; w < 16; ++w)
+            for (int b = 0; b < 8; ++b) buf[64 * nb - 8 + b] = (uint8_t)(bits >> (8 * b));
+            uint32_t M[32];
+            for (int w = 0; w < 32; ++w)
                 M[w] = (uint32_t)buf[4 * w] | ((uint32_t)buf[4 * w + 1] << 8) | ((uint32_t)buf[4 * w + 2] << 16) |
                        ((uint32_t)buf[4 * w + 3] << 24);
-            __m512i mv[16][NV];
+            __m512i mv[16][NV], mv2[16][NV];
             for (int w = 0; w < 16; ++w)
                 for (int v = 0; v < NV; ++v) mv[w][v] = _mm512_set1_epi32((int)M[w]);
-            const int wt = (int)(p / 4), sh = (int)(8 * (p % 4));
+            if (nb == 2)
+                for (int w = 0; w < 16; ++w)
+                    for (int v = 0; v < NV; ++v) mv2[w][v] = _mm512_set1_epi32((int)M[16 + w]);
+            const int wt = (int)(p / 4), sh = (int)(8 * (p % 4)); /* p <= 63: the thread byte is in the first block */
             for (int rep = 0; rep < 256 / (16 * NV); ++rep) {
                 for (int v = 0; v < NV; ++v) {
                     __m512i tb = _mm512_add_epi32(lane, _mm512_set1_epi32(16 * (NV * rep + v)));
                     mv[wt][v] = _mm512_add_epi32(_mm512_set1_epi32((int)M[wt]), _mm512_slli_epi32(tb, (unsigned)sh));
                 }
-                __m512i a[NV], b[NV], c[NV], d[NV];
+                __m512i st[4][NV];
+                for (int w = 0; w < 4; ++w)
+                    for (int v = 0; v < NV; ++v) st[w][v] = _mm512_set1_epi32((int)j->iv[w]);
+                block_vec(st, mv);
+                if (nb == 2) block_vec(st, mv2);
                 for (int v = 0; v < NV; ++v) {
-                    a[v] = _mm512_set1_epi32((int)j->iv[0]);
-                    b[v] = _mm512_set1_epi32((int)j->iv[1]);
-                    c[v] = _mm512_set1_epi32((int)j->iv[2]);
-                    d[v] = _mm512_set1_epi32((int)j->iv[3]);
-                }
-#define R4(tt, r, i0, w0, w1, w2, w3)                       \
-    STEP(a, b, c, d, tt, mv[w0], i0 + 0, S[r][0]);          \
-    STEP(d, a, b, c, tt, mv[w1], i0 + 1, S[r][1]);          \
-    STEP(c, d, a, b, tt, mv[w2], i0 + 2, S[r][2]);          \
-    STEP(b, c, d, a, tt, mv[w3], i0 + 3, S[r][3]);
-                R4(TF, 0, 0, 0, 1, 2, 3) R4(TF, 0, 4, 4, 5, 6, 7) R4(TF, 0, 8, 8, 9, 10, 11)
-                R4(TF, 0, 12, 12, 13, 14, 15)
-                R4(TG, 1, 16, 1, 6, 11, 0) R4(TG, 1, 20, 5, 10, 15, 4) R4(TG, 1, 24, 9, 14, 3, 8)
-                R4(TG, 1, 28, 13, 2, 7, 12)
-                R4(TH, 2, 32, 5, 8, 11, 14) R4(TH, 2, 36, 1, 4, 7, 10) R4(TH, 2, 40, 13, 0, 3, 6)
-                R4(TH, 2, 44, 9, 12, 15, 2)
-                R4(TI, 3, 48, 0, 7, 14, 5) R4(TI, 3, 52, 12, 3, 10, 1) R4(TI, 3, 56, 8, 15, 6, 13)
-                R4(TI, 3, 60, 4, 11, 2, 9)
-#undef R4
-                for (int v = 0; v < NV; ++v) {
-                    const __m512i A = _mm512_add_epi32(a[v], _mm512_set1_epi32((int)j->iv[0]));
-                    const __m512i B = _mm512_add_epi32(b[v], _mm512_set1_epi32((int)j->iv[1]));
-                    const __m512i C = _mm512_add_epi32(c[v], _mm512_set1_epi32((int)j->iv[2]));
-                    const __m512i D = _mm512_add_epi32(d[v], _mm512_set1_epi32((int)j->iv[3]));
+                    const __m512i A = st[0][v], B = st[1][v], C = st[2][v], D = st[3][v];
                     __mmask16 z = _mm512_testn_epi32_mask(D, _mm512_set1_epi32((int)j->mask[3]));
                     if (j->mask[2]) z &= _mm512_testn_epi32_mask(C, _mm512_set1_epi32((int)j->mask[2]));
                     if (j->mask[1]) z &= _mm512_testn_epi32_mask(B, _mm512_set1_epi32((int)j->mask[1]));
@@ -269,12 +292,6 @@ int main(int argc, char **argv) {
     j.all = argc == 7;
     if (j.k_end > (1ull << 55) - 1 || j.k_begin > j.k_end) {
         fprintf(stderr, "fast_scan: bad k window (k < 2^55 - 1)\n");
-        return 2;
-    }
-    size_t clen_max = 0;
-    for (uint64_t x = j.k_end ? j.k_end - 1 : 0; x; x >>= 8) ++clen_max;
-    if (j.nonce_len % 64 + 1 + clen_max + 9 > 64) {
-        fprintf(stderr, "fast_scan: the nonce's tail, thread byte, chunk and padding must fit one block\n");
         return 2;
     }
     j.iv[0] = 0x67452301, j.iv[1] = 0xefcdab89, j.iv[2] = 0x98badcfe, j.iv[3] = 0x10325476;

@@ -54,7 +54,39 @@ Every case is also checked against SURVEY.md Appendix A where the survey lists i
     entry.  A case that misses is lengthened in 16-segment steps up to 64
     segments, then its seeded nonce is replaced.
 
-Usage:  python tests/golden/gen_golden.py [--big] | --deep | --seg-inner
+  * --layouts: tests/golden/layout_deep_hits.json, all-hits lists (the same
+    [[g, tz], ...] form, ntz 8, workerBits = 0) for every specialised layout
+    <NBLK, W0, SH> of md5_search_kernel.h, so that each layout's N >= 8 test
+    and its N > 8 full_check are pinned to lists this library had no part in.
+    CPU only.  It reads tests/golden/layout_hints.json (tools/layout_hints.py,
+    run on the GPU): per case a nonce and one index with >= 9 trailing zeroes
+    (8 where the case allows it), found by walking N = 8 hits and checking them
+    with hashlib, or by the batch kernel for the tiny k ranges.  A hint is only
+    a place to look: it is re-hashed, and the fixture takes the nonce and the
+    window's position from it, nothing else.  The window is
+    [(s - 1) 2^24 + u, (s + 1) 2^24) with s the hint's 2^24-k segment and u a
+    seeded offset below 2^20, clipped to the k of the hint's chunk length (one
+    layout per window); the tiny ranges (<1,12,3>, <1,13,0>, <1,13,1>, the
+    "_ls" cases below k = 2^16) are scanned whole.  Each case is {name, nonce,
+    k_begin, k_end, nblk, w0, sh, deep, hits}; deep says the list has a
+    tz >= 9 entry.  <1,13,2> and <1,13,3> have no md5 launch (only k = 0 fits
+    one block, or nothing does) and are named under "unreachable".
+    fast_scan.c's two-final-block layout (p + 1 + L + 9 > 64) is cross-checked
+    before it is used:
+      - all-hits and first-hit modes against the byte-wise C oracle walked hit
+        by hit, for seeded nonces of 48 ... 63 and 112 ... 127 bytes, on windows
+        across k = 256, 65536 and 2^24 (where some of these lengths go from one
+        block to two) at ntz 3, 4 and 5;
+      - first-hit mode reproduces every two-block golden of pow_golden.json
+        (first_hits, nonce_lengths).
+    Asserted before the file is written: the hint is in its list; every entry
+    re-hashes (hashlib) to its tz; every case but b1w13s1 / ls1 / ls2 has a
+    tz >= 9 entry; at least a third of the chunk-length-4 cases have their
+    first tz >= 9 entry in the window's second segment (reached with a
+    non-zero segment addition); the layouts of the cases and "unreachable"
+    are all 72.  The same hints give the same file, byte for byte.
+
+Usage:  python tests/golden/gen_golden.py [--big] | --deep | --seg-inner | --layouts
 """
 import argparse
 import ctypes
@@ -476,13 +508,127 @@ def seg_inner(path):
     print(f"--seg-inner: {time.time() - t_all:.0f} s", file=sys.stderr)
 
 
+# ---------------- --layouts: all-hits lists for every specialised layout ----------------
+LAYOUT_NTZ = 8
+# layouts with no md5 launch: one final block only fits the chunk of zero bytes (k = 0, the k = 0 kernel)
+LAYOUT_UNREACHABLE = [
+    {"nblk": 1, "w0": 13, "sh": 2, "reason": "nonce length 54 mod 64: one block holds only k = 0 (54 + 1 + 0 + 9 = 64)"},
+    {"nblk": 1, "w0": 13, "sh": 3, "reason": "nonce length 55 mod 64: no k fits one block (55 + 1 + 0 + 9 = 65)"},
+]
+LAYOUT_MAY_BE_SHALLOW = ("b1w13s1", "ls1", "ls2")  # tz >= 9 not required (tools/layout_hints.py)
+
+
+def chunk_range(k):
+    """[lo, hi) of the k whose chunk is as long as k's (k >= 1), below DPOW_K_LIMIT."""
+    n = len(chunk_of(k))
+    return 1 << (8 * (n - 1)), min(1 << (8 * n), K_LIMIT)
+
+
+def layout_of(nonce_len, k):
+    """(nblk, w0, sh) of md5_search_kernel.h's layout for a candidate: final blocks behind the
+    midstate, the thread byte's word and byte in them."""
+    p = nonce_len % 64
+    return (2 if p + 1 + len(chunk_of(k)) + 9 > 64 else 1), p // 4, p % 4
+
+
+def layouts_crosscheck(exe, lib, golden):
+    """The scanner's two-final-block layout against the byte-wise oracle and the existing goldens."""
+    total = wins = 0
+    for ln in list(range(48, 64)) + list(range(112, 128)):
+        nonce = seeded_nonce(8000 + ln, ln)
+        for edge in (1 << 8, 1 << 16, 1 << 24):  # chunk lengths 1|2, 2|3, 3|4: one block | two for some of these
+            for ntz, half in ((3, 1 << 6), (4, 1 << 9), (5, 1 << 11)):
+                k0, k1 = max(0, edge - half), edge + half
+                got = fast_scan_all(exe, nonce, ntz, k0, k1)
+                exp = oracle_all_hits(lib, nonce, ntz, k0, k1)
+                assert got == exp, (ln, ntz, k0, k1, got[:4], exp[:4])
+                assert all(tz_of(nonce, g) == tz for g, tz in got)
+                first = fast_scan_window(exe, nonce, ntz, k0, k1)
+                assert first == (exp[0][0] if exp else None), (ln, ntz, k0, k1, first)
+                total += len(got)
+                wins += 1
+    assert total >= wins  # about 8, 4 and 1 hits per window
+    print("two-block all-hits and first-hit modes agree with the oracle walk on", wins, "windows,", total, "hits",
+          file=sys.stderr)
+    n = 0
+    for e in golden["first_hits"] + golden["nonce_lengths"]:
+        k = e["global_idx"] >> 8
+        if layout_of(len(e["nonce"]), k)[0] == 2:
+            assert fast_scan_window(exe, e["nonce"], e["ntz"], 0, k + 2) == e["global_idx"], e
+            n += 1
+    assert n >= 10, n
+    print("first-hit mode reproduces", n, "existing two-block goldens", file=sys.stderr)
+
+
+def layouts(path):
+    """tests/golden/layout_deep_hits.json from tests/golden/layout_hints.json (see the module docstring)."""
+    import time
+    t_all = time.time()
+    with open(os.path.join(HERE, "pow_golden.json")) as f:
+        golden = json.load(f)
+    with open(os.path.join(HERE, "layout_hints.json")) as f:
+        hints = json.load(f)["hints"]
+    exe = build_fast_scan()
+    lib = load_oracle()
+    layouts_crosscheck(exe, lib, golden)
+    print(f"cross-checks: {time.time() - t_all:.0f} s", file=sys.stderr)
+    cases = []
+    for h in hints:
+        name, nonce, g = h["name"], h["nonce"], h["global_idx"]
+        assert tz_of(nonce, g) >= LAYOUT_NTZ, (name, "the hint does not re-hash")
+        k = g >> 8
+        lo, hi = chunk_range(k)
+        if h["whole_range"]:  # a tiny k range: all of it
+            k0, k1 = h["k_lo"], h["k_hi"]
+            assert 1 <= k0 < k1 <= 1 << 24, (name, k0, k1)
+        else:
+            s = k // SEG
+            u = random.Random(f"layouts/{name}").randrange(1 << 20)
+            k0, k1 = max((s - 1) * SEG + u, lo), min((s + 1) * SEG, hi)
+        assert 1 <= k0 <= k < k1 <= K_LIMIT, (name, k0, k, k1)
+        lay = layout_of(len(nonce), k0)
+        assert lay == layout_of(len(nonce), k1 - 1) == layout_of(len(nonce), k), (name, "one layout per window")
+        t = time.time()
+        hits = fast_scan_all(exe, nonce, LAYOUT_NTZ, k0, k1)
+        gs = [x for x, _ in hits]
+        assert g in gs, (name, "the hint is not in the list")
+        assert gs == sorted(set(gs)) and all(k0 <= x >> 8 < k1 for x in gs), name
+        for x, tz in hits:
+            assert tz >= LAYOUT_NTZ and tz_of(nonce, x) == tz, (name, x, tz)
+        deep_case = any(tz >= 9 for _, tz in hits)
+        assert deep_case or name in LAYOUT_MAY_BE_SHALLOW, (name, "no tz >= 9 entry")
+        cases.append({"name": name, "nonce": list(nonce), "k_begin": k0, "k_end": k1, "nblk": lay[0], "w0": lay[1],
+                      "sh": lay[2], "deep": deep_case, "hits": hits})
+        print(f"{name}: <{lay[0]},{lay[1]},{lay[2]}> [{k0}, {k1}) {len(hits)} entries, "
+              f"{sum(tz >= 9 for _, tz in hits)} with tz >= 9 ({time.time() - t:.0f} s)", file=sys.stderr)
+    # chunk length 4: the first tz >= 9 entry in the window's second segment (a non-zero segment
+    # addition in the launch that reaches it) for at least a third
+    l4 = [c for c in cases if c["name"].startswith("len")]
+    second = [c["name"] for c in l4
+              if (next(x for x, tz in c["hits"] if tz >= 9) >> 8) // SEG > c["k_begin"] // SEG]
+    assert len(l4) == 64 and 3 * len(second) >= len(l4), (len(second), len(l4))
+    have = {(c["nblk"], c["w0"], c["sh"]) for c in cases} | {(u["nblk"], u["w0"], u["sh"]) for u in LAYOUT_UNREACHABLE}
+    assert len(have) == 72, sorted(have)
+    with open(path, "w") as f:
+        json.dump({"ntz": LAYOUT_NTZ, "unreachable": LAYOUT_UNREACHABLE, "cases": cases}, f, indent=0,
+                  separators=(",", ":"))
+        f.write("\n")
+    print(f"--layouts: {len(cases)} cases, {len(second)} of {len(l4)} chunk-length-4 cases with their first "
+          f"tz >= 9 entry in the second segment, {time.time() - t_all:.0f} s", file=sys.stderr)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--layouts", action="store_true",
+                    help="write layout_deep_hits.json from layout_hints.json: all-hits lists per layout (fast_scan)")
     ap.add_argument("--big", action="store_true", help="also compute N=7/8 cases via the C oracle")
     ap.add_argument("--deep", action="store_true", help="add N=9/10 hits (fast_scan) to the existing file")
     ap.add_argument("--seg-inner", action="store_true",
                     help="write seg_inner_hits.json: all-hits lists for the segment-inner kernels (fast_scan)")
     args = ap.parse_args()
+    if args.layouts:
+        layouts(os.path.join(HERE, "layout_deep_hits.json"))
+        return
     if args.seg_inner:
         seg_inner(os.path.join(HERE, "seg_inner_hits.json"))
         return
