@@ -13,16 +13,15 @@
 #include <time.h>
 
 #include <algorithm>
-#include <chrono>
 #include <string>
 #include <vector>
 
 #include "../../include/dpow.h"
 #include "../../include/dpow_worker.h"
 #include "batch.h"
+#include "ctx.h"
 #include "md5_batch.h"
 #include "md5_host.h"
-#include "node.h"
 #include "plan.h"
 
 namespace dpow {
@@ -31,11 +30,6 @@ namespace {
 
 uint64_t pow2_floor(uint64_t x) { return x ? 1ull << (63 - __builtin_clzll(x)) : 0; }
 uint64_t pow2_ceil(uint64_t x) { return x <= 1 ? 1 : pow2_floor(x - 1) << 1; }
-
-int64_t now_ns() {
-    return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch())
-        .count();
-}
 
 // Midstate, final-block template and partition of one task.
 void fill_task(BatchTask &t, const uint8_t *nonce, size_t nonce_len, uint32_t ntz, uint32_t worker_byte,
@@ -113,14 +107,10 @@ constexpr size_t kOutOff = kMapOff + DPOW_BATCH_MAX * sizeof(BatchEntry);
 constexpr size_t kRecOff = kOutOff + DPOW_BATCH_MAX * sizeof(unsigned long long);
 constexpr size_t kHostBytes = kRecOff + 64;
 
-int hip_fail(hipError_t e, const char *what) {
-    return fail(DPOW_EHIP, (std::string(what) + ": " + hipGetErrorString(e)).c_str());
-}
-
 int batch_state(BatchState **state, hipStream_t stream) {
     if (*state) return 0;
     BatchState *s = new (std::nothrow) BatchState();
-    if (!s) return fail(DPOW_ENOMEM, "dpow_search_batch: out of memory");
+    if (!s) return set_error(DPOW_ENOMEM, "dpow_search_batch: out of memory");
     hipError_t e;
     if ((e = hipMalloc(&s->d_mem, kDevBytes)) != hipSuccess ||
         (e = hipHostMalloc(&s->h_mem, kHostBytes, hipHostMallocCoherent | hipHostMallocMapped)) != hipSuccess ||
@@ -144,12 +134,9 @@ int wait_record(const BatchRecord *rec, uint32_t seq, hipStream_t stream) {
         if (__atomic_load_n(&rec->seq, __ATOMIC_ACQUIRE) == seq) return 0;
         const bool spinning = now_ns() - t0 < 200000;
         if (spinning ? (it % 4096 == 0) : (it % 16 == 0)) {
-            const hipError_t q = hipStreamQuery(stream);
-            if (q == hipSuccess) {
-                if (__atomic_load_n(&rec->seq, __ATOMIC_ACQUIRE) == seq) return 0;
-                return fail(DPOW_EHIP, "dpow_search_batch: stream idle without the launch's completion record");
-            }
-            if (q != hipErrorNotReady) return hip_fail(q, "hipStreamQuery");
+            const int alive = stream_liveness(stream, &rec->seq, seq,
+                                              "dpow_search_batch: stream idle without the launch's completion record");
+            if (alive != 0) return alive < 0 ? alive : 0;
         }
         if (spinning) {
             __builtin_ia32_pause();
@@ -161,11 +148,11 @@ int wait_record(const BatchRecord *rec, uint32_t seq, hipStream_t stream) {
 }
 
 int check_task(const dpow_batch_task &t) {
-    if (t.nonce_len && !t.nonce) return fail(DPOW_EINVAL, "dpow_search_batch: nonce is NULL");
-    if (t.nonce_len > DPOW_MAX_NONCE) return fail(DPOW_EINVAL, "dpow_search_batch: nonce longer than DPOW_MAX_NONCE");
-    if (t.worker_byte > 255u) return fail(DPOW_EINVAL, "dpow_search_batch: worker_byte > 255");
-    if (t.k_begin > t.k_end) return fail(DPOW_EINVAL, "dpow_search_batch: k_begin > k_end");
-    if (t.k_end > DPOW_K_LIMIT) return fail(DPOW_ERANGE, "dpow_search_batch: k_end beyond DPOW_K_LIMIT");
+    if (t.nonce_len && !t.nonce) return set_error(DPOW_EINVAL, "dpow_search_batch: nonce is NULL");
+    if (t.nonce_len > DPOW_MAX_NONCE) return set_error(DPOW_EINVAL, "dpow_search_batch: nonce longer than DPOW_MAX_NONCE");
+    if (t.worker_byte > 255u) return set_error(DPOW_EINVAL, "dpow_search_batch: worker_byte > 255");
+    if (t.k_begin > t.k_end) return set_error(DPOW_EINVAL, "dpow_search_batch: k_begin > k_end");
+    if (t.k_end > DPOW_K_LIMIT) return set_error(DPOW_ERANGE, "dpow_search_batch: k_end beyond DPOW_K_LIMIT");
     return 0;
 }
 
@@ -179,9 +166,9 @@ void batch_free(BatchState *s) {
 }
 
 int batch_check(const dpow_batch_task *tasks, size_t n_tasks) {
-    if (!tasks) return fail(DPOW_EINVAL, "dpow_search_batch: tasks is NULL");
+    if (!tasks) return set_error(DPOW_EINVAL, "dpow_search_batch: tasks is NULL");
     if (n_tasks == 0 || n_tasks > DPOW_BATCH_MAX)
-        return fail(DPOW_EINVAL, "dpow_search_batch: n_tasks must be in [1, DPOW_BATCH_MAX]");
+        return set_error(DPOW_EINVAL, "dpow_search_batch: n_tasks must be in [1, DPOW_BATCH_MAX]");
     for (size_t i = 0; i < n_tasks; ++i) {
         const int rc = check_task(tasks[i]);
         if (rc < 0) return rc;
@@ -277,7 +264,7 @@ int batch_run(BatchState **state, hipStream_t stream, const volatile uint32_t *c
                 size_t len = 0;
                 dpow_secret_from_index(b, sec, &len);
                 if (!dpow_verify(t.nonce, t.nonce_len, sec, len, t.ntz))
-                    return fail(DPOW_EVERIFY, "dpow_search_batch: kernel hit failed host MD5 verification");
+                    return set_error(DPOW_EVERIFY, "dpow_search_batch: kernel hit failed host MD5 verification");
                 status[l.task] = DPOW_FOUND;
                 hit[l.task] = b;
                 continue;
@@ -305,11 +292,11 @@ extern "C" {
 int dpow_batch_candidate(const uint8_t *nonce, size_t nonce_len, uint32_t worker_byte, uint32_t worker_bits,
                          uint64_t local_idx, uint32_t iv_out[4], uint32_t words_out[32], uint32_t *nblk_out) {
     if (!iv_out || !words_out || !nblk_out || (nonce_len && !nonce))
-        return fail(DPOW_EINVAL, "dpow_batch_candidate: NULL argument");
+        return set_error(DPOW_EINVAL, "dpow_batch_candidate: NULL argument");
     if (nonce_len > DPOW_MAX_NONCE || worker_byte > 255u)
-        return fail(DPOW_EINVAL, "dpow_batch_candidate: bad nonce length or worker_byte");
+        return set_error(DPOW_EINVAL, "dpow_batch_candidate: bad nonce length or worker_byte");
     if ((local_idx >> remainder_bits(worker_bits)) >= DPOW_K_LIMIT)
-        return fail(DPOW_ERANGE, "dpow_batch_candidate: k beyond DPOW_K_LIMIT");
+        return set_error(DPOW_ERANGE, "dpow_batch_candidate: k beyond DPOW_K_LIMIT");
     BatchTask t;
     fill_task(t, nonce, nonce_len, 0, worker_byte, worker_bits);
     for (int w = 0; w < 4; ++w) iv_out[w] = t.iv[w];
@@ -320,13 +307,13 @@ int dpow_batch_candidate(const uint8_t *nonce, size_t nonce_len, uint32_t worker
 int dpow_batch_plan(const uint64_t *k_begin, const uint64_t *k_end, const uint32_t *worker_bits, size_t n_tasks,
                     dpow_batch_range *out, size_t max_entries, uint64_t *launches_out) {
     if (!k_begin || !k_end || !worker_bits || !launches_out)
-        return fail(DPOW_EINVAL, "dpow_batch_plan: NULL argument");
+        return set_error(DPOW_EINVAL, "dpow_batch_plan: NULL argument");
     if (n_tasks == 0 || n_tasks > DPOW_BATCH_MAX)
-        return fail(DPOW_EINVAL, "dpow_batch_plan: n_tasks must be in [1, DPOW_BATCH_MAX]");
+        return set_error(DPOW_EINVAL, "dpow_batch_plan: n_tasks must be in [1, DPOW_BATCH_MAX]");
     std::vector<Live> live, next;
     for (size_t i = 0; i < n_tasks; ++i) {
-        if (k_begin[i] > k_end[i]) return fail(DPOW_EINVAL, "dpow_batch_plan: k_begin > k_end");
-        if (k_end[i] > DPOW_K_LIMIT) return fail(DPOW_ERANGE, "dpow_batch_plan: k_end beyond DPOW_K_LIMIT");
+        if (k_begin[i] > k_end[i]) return set_error(DPOW_EINVAL, "dpow_batch_plan: k_begin > k_end");
+        if (k_end[i] > DPOW_K_LIMIT) return set_error(DPOW_ERANGE, "dpow_batch_plan: k_end beyond DPOW_K_LIMIT");
         const uint32_t rbits = remainder_bits(worker_bits[i]);
         if (k_begin[i] < k_end[i]) live.push_back(Live{(uint32_t)i, k_begin[i] << rbits, k_end[i] << rbits});
     }
@@ -349,7 +336,7 @@ int dpow_batch_plan(const uint64_t *k_begin, const uint64_t *k_end, const uint32
             if (entries[j].i_end < live[j].i_end) next.push_back(Live{live[j].task, entries[j].i_end, live[j].i_end});
         }
         live.swap(next);
-        if (n_out > (uint64_t)INT32_MAX) return fail(DPOW_ERANGE, "dpow_batch_plan: too many entries");
+        if (n_out > (uint64_t)INT32_MAX) return set_error(DPOW_ERANGE, "dpow_batch_plan: too many entries");
     }
     *launches_out = launch;
     return (int)n_out;
@@ -358,9 +345,9 @@ int dpow_batch_plan(const uint64_t *k_begin, const uint64_t *k_end, const uint32
 int dpow_batch_plan_block(const dpow_batch_range *entries, uint32_t n_live, uint32_t block, uint32_t *task,
                           uint64_t *lo, uint64_t *hi) {
     if (!entries || !task || !lo || !hi || n_live == 0)
-        return fail(DPOW_EINVAL, "dpow_batch_plan_block: bad argument");
+        return set_error(DPOW_EINVAL, "dpow_batch_plan_block: bad argument");
     const uint32_t row = block / n_live, j = block - row * n_live;
-    if (row >= entries[j].rows) return fail(DPOW_EINVAL, "dpow_batch_plan_block: block outside the launch's grid");
+    if (row >= entries[j].rows) return set_error(DPOW_EINVAL, "dpow_batch_plan_block: block outside the launch's grid");
     *task = entries[j].task;
     return batch_block_range(entries[j].i_begin, entries[j].i_end, row, entries[j].group, *lo, *hi) ? 1 : 0;
 }

@@ -29,12 +29,12 @@
 
 #include <time.h>
 
-#include <chrono>
 #include <new>
 #include <string>
 
 #include "../../include/dpow.h"
 #include "../../include/dpow_worker.h"
+#include "ctx.h"
 #include "node.h"
 
 namespace {
@@ -66,7 +66,7 @@ struct alignas(64) Entry {
     uint64_t joined;     // bit r: rank r has joined this task
     uint64_t nonce_len;
     uint64_t pad[4];
-    uint64_t dev_key[kMaxWorld];  // rank r's GPU (dpow::device_key; 0: unknown), written before its joined bit
+    uint64_t dev_key[kMaxWorld];  // rank r's GPU (dpow_ctx::dev_key; 0: unknown), written before its joined bit
     uint8_t nonce[DPOW_MAX_NONCE];
     dpow_node_slot slot;
     dpow_node_vote_entry votes[2 * kMaxWorld];
@@ -85,11 +85,6 @@ struct Layout {
 // DPOW_EPROTO instead of spinning forever.
 constexpr int64_t kLockTimeoutNs = 10ll * 1000000000ll;
 
-int64_t mono_ns() {
-    return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch())
-        .count();
-}
-
 class Lock {
    public:
     explicit Lock(uint32_t *w) : w_(w) {
@@ -105,7 +100,7 @@ class Lock {
                 continue;
             }
             sched_yield();
-            const int64_t t = mono_ns();
+            const int64_t t = dpow::now_ns();
             if (!t0) t0 = t;
             else if (t - t0 > kLockTimeoutNs) return;
         }
@@ -123,8 +118,8 @@ class Lock {
 };
 
 int lock_lost(const char *who) {
-    return dpow::fail(DPOW_EPROTO, (std::string(who) + ": the board's lock was held for 10 s (a worker process "
-                                                       "died inside a join or leave?)").c_str());
+    return dpow::set_error(DPOW_EPROTO, std::string(who) + ": the board's lock was held for 10 s (a worker process "
+                                                             "died inside a join or leave?)");
 }
 
 bool key_matches(const Entry &e, const uint8_t *nonce, size_t len, uint32_t ntz, uint32_t world) {
@@ -151,18 +146,18 @@ int same_gpu(const Entry &e, uint32_t world, uint64_t mine, const volatile uint3
 extern "C" {
 
 int dpow_board_open(const char *name, dpow_board **out) {
-    if (!out) return dpow::fail(DPOW_EINVAL, "dpow_board_open: out is NULL");
+    if (!out) return dpow::set_error(DPOW_EINVAL, "dpow_board_open: out is NULL");
     *out = nullptr;
     const size_t len = sizeof(Layout);
     dpow_board *b = new (std::nothrow) dpow_board();
-    if (!b) return dpow::fail(DPOW_ENOMEM, "dpow_board_open: out of memory");
+    if (!b) return dpow::set_error(DPOW_ENOMEM, "dpow_board_open: out of memory");
     void *m = MAP_FAILED;
     if (!name) {  // the workers of this process only
         m = mmap(nullptr, len, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
     } else {      // every worker process of this host that opens the same name
         if (name[0] != '/' || strchr(name + 1, '/')) {
             delete b;
-            return dpow::fail(DPOW_EINVAL, "dpow_board_open: name must be \"/name\" (one POSIX shm object)");
+            return dpow::set_error(DPOW_EINVAL, "dpow_board_open: name must be \"/name\" (one POSIX shm object)");
         }
         b->fd = shm_open(name, O_RDWR | O_CREAT, 0600);
         struct stat st;
@@ -171,7 +166,7 @@ int dpow_board_open(const char *name, dpow_board **out) {
             const std::string err = std::string("dpow_board_open: ") + name + ": " + strerror(errno);
             if (b->fd >= 0) close(b->fd);
             delete b;
-            return dpow::fail(DPOW_EINVAL, err.c_str());
+            return dpow::set_error(DPOW_EINVAL, err);
         }
         m = mmap(nullptr, len, PROT_READ | PROT_WRITE, MAP_SHARED, b->fd, 0);
         b->shared = true;
@@ -179,7 +174,7 @@ int dpow_board_open(const char *name, dpow_board **out) {
     if (m == MAP_FAILED) {
         if (b->fd >= 0) close(b->fd);
         delete b;
-        return dpow::fail(DPOW_ENOMEM, "dpow_board_open: mmap failed");
+        return dpow::set_error(DPOW_ENOMEM, "dpow_board_open: mmap failed");
     }
     b->mem = static_cast<Layout *>(m);
     uint64_t z = 0;
@@ -188,7 +183,7 @@ int dpow_board_open(const char *name, dpow_board **out) {
         munmap(m, len);
         if (b->fd >= 0) close(b->fd);
         delete b;
-        return dpow::fail(DPOW_EPROTO, "dpow_board_open: the shared object holds another board layout");
+        return dpow::set_error(DPOW_EPROTO, "dpow_board_open: the shared object holds another board layout");
     }
     *out = b;
     return 0;
@@ -207,15 +202,15 @@ void dpow_board_close(dpow_board *b) {
 }
 
 int dpow_board_unlink(const char *name) {
-    if (!name) return dpow::fail(DPOW_EINVAL, "dpow_board_unlink: name is NULL");
+    if (!name) return dpow::set_error(DPOW_EINVAL, "dpow_board_unlink: name is NULL");
     if (shm_unlink(name) != 0 && errno != ENOENT)
-        return dpow::fail(DPOW_EINVAL, (std::string("dpow_board_unlink: ") + strerror(errno)).c_str());
+        return dpow::set_error(DPOW_EINVAL, std::string("dpow_board_unlink: ") + strerror(errno));
     return 0;
 }
 
 int dpow_board_join(dpow_board *b, const uint8_t *nonce, size_t nonce_len, uint32_t ntz, uint32_t world,
                     uint32_t rank, dpow_node_slot **slot, dpow_node_vote_entry **votes) {
-    if (!slot || !votes) return dpow::fail(DPOW_EINVAL, "dpow_board_join: NULL argument");
+    if (!slot || !votes) return dpow::set_error(DPOW_EINVAL, "dpow_board_join: NULL argument");
     Entry *e = nullptr;
     const int rc = board_join(b, nonce, nonce_len, ntz, world, rank, 0, &e);
     if (rc < 0) return rc;
@@ -225,15 +220,15 @@ int dpow_board_join(dpow_board *b, const uint8_t *nonce, size_t nonce_len, uint3
 }
 
 int dpow_board_leave(dpow_board *b, dpow_node_slot *slot) {
-    if (!b || !b->mem || !slot) return dpow::fail(DPOW_EINVAL, "dpow_board_leave: NULL argument");
+    if (!b || !b->mem || !slot) return dpow::set_error(DPOW_EINVAL, "dpow_board_leave: NULL argument");
     Layout &L = *b->mem;
     const uintptr_t off = (uintptr_t)slot - (uintptr_t)&L.e[0].slot;
     if ((uintptr_t)slot < (uintptr_t)&L.e[0].slot || off % sizeof(Entry) != 0 || off / sizeof(Entry) >= kEntries)
-        return dpow::fail(DPOW_EINVAL, "dpow_board_leave: not a slot of this board");
+        return dpow::set_error(DPOW_EINVAL, "dpow_board_leave: not a slot of this board");
     Entry &e = L.e[off / sizeof(Entry)];
     Lock lk(&L.h.lock);
     if (!lk.held()) return lock_lost("dpow_board_leave");
-    if (e.state != 1 || e.refs == 0) return dpow::fail(DPOW_EPROTO, "dpow_board_leave: the entry is not joined");
+    if (e.state != 1 || e.refs == 0) return dpow::set_error(DPOW_EPROTO, "dpow_board_leave: the entry is not joined");
     // The last rank out frees the entry, whether or not every rank joined (a worker that
     // answered from its cache never does; the others left on their kill).
     if (--e.refs == 0) __atomic_store_n(&e.state, 0u, __ATOMIC_RELEASE);
@@ -241,7 +236,7 @@ int dpow_board_leave(dpow_board *b, dpow_node_slot *slot) {
 }
 
 int dpow_board_counters(dpow_board *b, uint64_t *tasks, uint64_t *shared_gpu) {
-    if (!b || !b->mem || !tasks || !shared_gpu) return dpow::fail(DPOW_EINVAL, "dpow_board_counters: NULL argument");
+    if (!b || !b->mem || !tasks || !shared_gpu) return dpow::set_error(DPOW_EINVAL, "dpow_board_counters: NULL argument");
     Lock lk(&b->mem->h.lock);
     if (!lk.held()) return lock_lost("dpow_board_counters");
     *tasks = b->mem->h.tasks;
@@ -250,7 +245,7 @@ int dpow_board_counters(dpow_board *b, uint64_t *tasks, uint64_t *shared_gpu) {
 }
 
 int dpow_board_tasks(dpow_board *b) {
-    if (!b || !b->mem) return dpow::fail(DPOW_EINVAL, "dpow_board_tasks: board is NULL");
+    if (!b || !b->mem) return dpow::set_error(DPOW_EINVAL, "dpow_board_tasks: board is NULL");
     Lock lk(&b->mem->h.lock);
     if (!lk.held()) return lock_lost("dpow_board_tasks");
     int n = 0;
@@ -262,13 +257,13 @@ int dpow_board_search(dpow_board *b, dpow_ctx *ctx, const uint8_t *nonce, size_t
                       uint32_t worker_byte, uint32_t worker_bits, uint64_t *best_global_idx,
                       uint8_t secret_out[DPOW_MAX_SECRET], size_t *secret_len, uint32_t *owner) {
     if (!b || !ctx || !best_global_idx || !secret_out || !secret_len || !owner)
-        return dpow::fail(DPOW_EINVAL, "dpow_board_search: NULL argument");
+        return dpow::set_error(DPOW_EINVAL, "dpow_board_search: NULL argument");
     *owner = 0;
     *secret_len = 0;
     if (worker_bits < 1 || (1u << worker_bits) > kMaxWorld || worker_byte >= (1u << worker_bits))
-        return dpow::fail(DPOW_EINVAL, "dpow_board_search: needs 1 <= worker_bits <= 6 and worker_byte < 2^worker_bits");
+        return dpow::set_error(DPOW_EINVAL, "dpow_board_search: needs 1 <= worker_bits <= 6 and worker_byte < 2^worker_bits");
     const uint32_t world = 1u << worker_bits;
-    const uint64_t key = dpow::device_key(ctx);
+    const uint64_t key = ctx->dev_key;
     Entry *e = nullptr;
     int rc = board_join(b, nonce, nonce_len, ntz, world, worker_byte, key, &e);
     if (rc < 0) return rc;
@@ -284,7 +279,7 @@ int dpow_board_search(dpow_board *b, dpow_ctx *ctx, const uint8_t *nonce, size_t
         if (same == DPOW_CANCELLED) dpow_node_stop(slot);
         const std::string err = same == DPOW_CANCELLED ? "" : dpow_last_error();
         (void)dpow_board_leave(b, slot);
-        return same == DPOW_CANCELLED ? DPOW_CANCELLED : dpow::fail(same, err.c_str());
+        return same == DPOW_CANCELLED ? DPOW_CANCELLED : dpow::set_error(same, err);
     }
     // DPOW_DIAG_BOARD_SPLIT=1: every rank searches its own partition even on a shared GPU (tests
     // cover the multi-GPU role on one GPU with it; dpow_diag.h)
@@ -294,13 +289,13 @@ int dpow_board_search(dpow_board *b, dpow_ctx *ctx, const uint8_t *nonce, size_t
     uint64_t epoch = 0;  // the entry's votes start at zero (board_join)
     uint32_t batches = 0;
     const uint64_t batch_k = kBatchCandidates >> (8 - worker_bits);
-    dpow::set_solo(ctx, role == 1);
+    ctx->solo = role == 1;  // no young-search sharing with the idle ranks (plan.h kYoungNs)
     rc = dpow::node_mine(ctx, slot, e->votes, worker_byte, world, &epoch, kVoteTimeoutNs, nonce, nonce_len, ntz, 0,
                          DPOW_K_LIMIT, 0, batch_k, best_global_idx, secret_out, secret_len, &batches, true, role);
-    dpow::set_solo(ctx, false);
+    ctx->solo = false;
     const std::string err = rc < 0 ? dpow_last_error() : "";
     (void)dpow_board_leave(b, slot);
-    if (rc < 0) return dpow::fail(rc, err.c_str());
+    if (rc < 0) return dpow::set_error(rc, err);
     if (rc == DPOW_FOUND) *owner = (((uint32_t)*best_global_idx & 0xFFu) >> (8 - worker_bits)) == worker_byte ? 1u : 0u;
     return rc;
 }
@@ -311,10 +306,10 @@ namespace {
 
 int board_join(dpow_board *b, const uint8_t *nonce, size_t nonce_len, uint32_t ntz, uint32_t world, uint32_t rank,
                uint64_t dev_key, Entry **out) {
-    if (!b || !b->mem || (nonce_len && !nonce)) return dpow::fail(DPOW_EINVAL, "dpow_board_join: NULL argument");
-    if (nonce_len > DPOW_MAX_NONCE) return dpow::fail(DPOW_EINVAL, "dpow_board_join: nonce too long");
+    if (!b || !b->mem || (nonce_len && !nonce)) return dpow::set_error(DPOW_EINVAL, "dpow_board_join: NULL argument");
+    if (nonce_len > DPOW_MAX_NONCE) return dpow::set_error(DPOW_EINVAL, "dpow_board_join: nonce too long");
     if (world < 2 || world > kMaxWorld || (world & (world - 1)) != 0 || rank >= world)
-        return dpow::fail(DPOW_EINVAL, "dpow_board_join: world must be a power of two in [2, 64], rank < world");
+        return dpow::set_error(DPOW_EINVAL, "dpow_board_join: world must be a power of two in [2, 64], rank < world");
     Layout &L = *b->mem;
     const uint64_t bit = 1ull << rank;
     Lock lk(&L.h.lock);
@@ -334,7 +329,7 @@ int board_join(dpow_board *b, const uint8_t *nonce, size_t nonce_len, uint32_t n
         }
         if (e.state == 0 && !free_e) free_e = &e;
     }
-    if (!free_e) return dpow::fail(DPOW_ENOMEM, "dpow_board_join: every task entry of the board is in use");
+    if (!free_e) return dpow::set_error(DPOW_ENOMEM, "dpow_board_join: every task entry of the board is in use");
     Entry &e = *free_e;
     e.ntz = ntz;
     e.world = world;
@@ -359,7 +354,7 @@ int board_join(dpow_board *b, const uint8_t *nonce, size_t nonce_len, uint32_t n
 // GPU is seen, "yes" needs the full set of W keys, which all ranks then read alike.
 int same_gpu(const Entry &e, uint32_t world, uint64_t mine, const volatile uint32_t *cancel) {
     const uint64_t full = world == 64 ? ~0ull : (1ull << world) - 1;
-    const int64_t t0 = mono_ns();
+    const int64_t t0 = dpow::now_ns();
     for (uint64_t it = 0;; ++it) {
         const uint64_t m = __atomic_load_n(&e.joined, __ATOMIC_ACQUIRE);
         for (uint32_t r = 0; r < world; ++r)
@@ -370,9 +365,9 @@ int same_gpu(const Entry &e, uint32_t world, uint64_t mine, const volatile uint3
             __builtin_ia32_pause();
             continue;
         }
-        const int64_t t = mono_ns();
+        const int64_t t = dpow::now_ns();
         if (t - t0 > kVoteTimeoutNs)
-            return dpow::fail(DPOW_EPROTO, "dpow_board_search: the task's other ranks never joined the board");
+            return dpow::set_error(DPOW_EPROTO, "dpow_board_search: the task's other ranks never joined the board");
         const struct timespec d = {0, 2000};
         nanosleep(&d, nullptr);
     }

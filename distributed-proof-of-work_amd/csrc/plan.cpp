@@ -428,6 +428,20 @@ bool cap_shared_launch(WindowPlanner &planner, PlannedLaunch &pl, uint64_t activ
     return true;
 }
 
+int size_window_launch(WindowPlanner &planner, PlannedLaunch &pl, uint32_t ntz, uint64_t cus, uint64_t active,
+                       const LaunchKnobs &knobs, uint64_t *worker_blocks, bool *seg_inner, bool recut) {
+    cap_shared_launch(planner, pl, active, knobs);
+    *seg_inner = seg_inner_select(planner, pl, ntz, knobs.seg_inner);
+    int rc = size_search_launch(pl, ntz, cus, grid_share(active, knobs), knobs, worker_blocks, active);
+    if (rc < 0 || !*seg_inner) return rc;
+    if (recut) return seg_inner_size(pl, *worker_blocks, worker_blocks);
+    PlannedLaunch cut = pl;
+    uint64_t wb = *worker_blocks;
+    rc = seg_inner_size(cut, wb, &wb);
+    pl.L.n_seg = cut.L.n_seg;
+    return rc;
+}
+
 uint64_t launch_blocks_per_cu(uint64_t candidates, uint32_t ntz, uint32_t rbits, uint64_t share) {
     // Small grids for short launches: candidates of this partition expected before its first hit: 16^N R / 256, and the
     // launch's, in device time (times the searches sharing the device; saturating).

@@ -197,18 +197,19 @@ uint64_t launch_claims_per_wave(uint32_t ntz, uint32_t rbits);
 #define DPOW_BLOCKS_PER_CU 6
 #endif
 constexpr uint64_t kMaxBlocksPerCu = DPOW_BLOCKS_PER_CU;
-// share: searches in flight on the device (dpow_api.cpp g_active).  Such a search runs at
+// share: searches in flight on the device (search.cpp g_active).  Such a search runs at
 // 1/share of the device, so the tiers judge its launch by device time: candidates and the
 // expected first hit times share.  BASELINE config 4 (8 logical workers on one GPU, N = 8,
 // 2^29 expected each) keeps the full grid.
 uint64_t launch_blocks_per_cu(uint64_t candidates, uint32_t ntz, uint32_t rbits, uint64_t share = 1);
 
-// The whole sizing of one dpow_search launch, shared by dpow_search and the geometry
-// diagnostic (dpow_diag_launch_geometry), so the diagnostic checks the grids searches run:
-// the device share of cus x launch_blocks_per_cu workgroups (at least one per claim
-// counter), size_launch with the ntz-dependent expected first hit, minimum chunk and
-// claims per wave, and the poll group (L.poll_wb).  Non-zero knobs override the policy
-// (the DPOW_DIAG_* A/B environment of dpow_open).
+// The whole sizing of one dpow_search launch is size_window_launch (below), which dpow_search
+// (search.cpp) and the geometry diagnostics (diag.cpp) both call, so the diagnostics check the
+// grids searches run.  Its size_search_launch step: the device share of cus x
+// launch_blocks_per_cu workgroups (at least one per claim counter), size_launch with the
+// ntz-dependent expected first hit, minimum chunk and claims per wave, and the poll group
+// (L.poll_wb).  Non-zero knobs override the policy (the DPOW_DIAG_* A/B environment of
+// dpow_open).
 struct LaunchKnobs {
     uint32_t bpc = 0, min_chunk = 0, cpw = 0, poll_wb = 0;
     int seg_inner = -1;            // segment-inner launches: -1 the policy, 0 never, 1 wherever the shape permits
@@ -220,7 +221,7 @@ struct LaunchKnobs {
 int size_search_launch(PlannedLaunch &pl, uint32_t ntz, uint64_t cus, uint64_t share, const LaunchKnobs &knobs,
                        uint64_t *worker_blocks, uint64_t active = 1);
 
-// Searches sharing a device (dpow_api.cpp g_active): the coordinator mirror's logical workers
+// Searches sharing a device (search.cpp g_active): the coordinator mirror's logical workers
 // on one GPU (BASELINE configs 3-5: 4 or 8 workers per GPU in the 1-GPU bench).
 //  - A grid is sized once per launch, so while the device is shared a launch lasts about
 //    kShareLaunchNs at 1/active of the device's rate (cap_shared_launch): grids follow searches
@@ -243,7 +244,7 @@ int size_search_launch(PlannedLaunch &pl, uint32_t ntz, uint64_t cus, uint64_t s
 #endif
 constexpr uint64_t kShareMax = DPOW_SHARE_MAX;
 // A search younger than kYoungNs that is alone on its device while other contexts of its
-// process were used there within kRecentNs (opened, or a search started: dpow_api.cpp
+// process were used there within kRecentNs (opened, or a search started: search.cpp
 // recent_contexts) plans its launches for all of them: searches that start together -- the
 // coordinator mirror's workers -- then share the device from their first launch, instead of
 // the first to register taking one uncapped full-device launch (round 4).  Contexts idle in a
@@ -281,5 +282,18 @@ int seg_inner_size(PlannedLaunch &pl, uint64_t max_blocks, uint64_t *worker_bloc
 // Re-plans pl (the launch planner.next() last returned) to at most kShareLaunchNs of hashing
 // when active > 1; returns whether it did.
 bool cap_shared_launch(WindowPlanner &planner, PlannedLaunch &pl, uint64_t active, const LaunchKnobs &knobs);
+
+// One launch of a window as dpow_search runs it, in one place: pl (the md5 launch planner.next()
+// last returned) is capped for a device shared by `active` searches (cap_shared_launch), taken
+// segment-inner or not (seg_inner_select, mode knobs.seg_inner; either may re-plan pl), sized
+// for 1/grid_share(active) of a device of `cus` CUs (size_search_launch) and, when segment-inner,
+// re-cut (seg_inner_size).  *worker_blocks: the launch's worker workgroups; *seg_inner: whether
+// it runs segment-inner.  recut = false (dpow_diag_launch_geometry) leaves a segment-inner
+// launch's claims as size_search_launch cut them, in index order, with only L.n_seg of the
+// re-cut.  Returns 0 or a negative DPOW_E* code.
+__attribute__((visibility("hidden"))) int size_window_launch(WindowPlanner &planner, PlannedLaunch &pl, uint32_t ntz,
+                                                             uint64_t cus, uint64_t active, const LaunchKnobs &knobs,
+                                                             uint64_t *worker_blocks, bool *seg_inner,
+                                                             bool recut = true);
 
 }  // namespace dpow

@@ -753,7 +753,7 @@ def _stopped_by_node(miner, lib, addr):
 
 def test_two_contexts_share_a_slot_one_closes(miner, golden):
     """the slot's host page is registered once per process and held by
-    every context that attached it (dpow_api.cpp page registry).  Two contexts attach one
+    every context that attached it (node.cpp page registry).  Two contexts attach one
     slot; closing one must not unregister the page under the other, whose kernels' watcher
     still stops at the node's stop and bound.  dpow_node_release refuses while a context is
     attached and, once detached, drops the registration; attaching again registers afresh."""
@@ -830,7 +830,7 @@ def test_early_found_fan_out(miner, golden):
 
 def test_concurrent_searches_share_the_gpu(golden):
     """Four contexts searching at once on one GPU (each sizes its grids to its share of the
-    device, dpow_api.cpp ActiveSearch): every answer is still the golden, and a concurrent
+    device, search.cpp ActiveSearch): every answer is still the golden, and a concurrent
     unreachable search is cancelled without disturbing the others."""
     cases = [([1, 2, 3, 4], 7), ([2, 2, 2, 2], 8), ([5, 6, 7, 8], 5), ([1, 2, 3, 4], 8)]
     exp = {(tuple(e["nonce"]), e["ntz"]): e for e in golden["first_hits"]}

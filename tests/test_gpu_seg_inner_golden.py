@@ -368,12 +368,12 @@ def test_bound_lowered_while_the_launch_runs(forced, board, wbits, ji, path):
 
     P = h and P below h give EXHAUSTED when P is in place before the search decides, as
     test_search_returns_at_covered_bound_vs_oracle asserts for a bound posted before the start.
-    dpow_api.cpp allows these other outcomes, and no more:
+    search.cpp allows these other outcomes, and no more:
       - the post lands after consume()'s last look (poll_node at its top, the ext_bound load
         beside `sn.best >= eb`): FOUND h.  Observable: the post's time against the decided time
         (dpow_diag_search_times[3]); within kMarginNs (1 ms, 5 ms for the poster thread's
         scheduled time) before it either outcome is legal.
-      - dpow_search_bound before the search opened its window (BoundWindow in search_window: "no
+      - dpow_search_bound before the search opened its window (Search::open_bound_window in search_window: "no
         search in flight") applies to nothing: FOUND h.  Required when the call ended before the
         search call began; either outcome until the first md5 launch was queued.
       - P = h through the node slot: h is a hit of this partition, so when the watcher relays it to
