@@ -26,14 +26,12 @@
 
 namespace dpow {
 
-namespace {
-
 uint64_t pow2_floor(uint64_t x) { return x ? 1ull << (63 - __builtin_clzll(x)) : 0; }
 uint64_t pow2_ceil(uint64_t x) { return x <= 1 ? 1 : pow2_floor(x - 1) << 1; }
 
 // Midstate, final-block template and partition of one task.
-void fill_task(BatchTask &t, const uint8_t *nonce, size_t nonce_len, uint32_t ntz, uint32_t worker_byte,
-               uint32_t worker_bits) {
+void batch_fill_task(BatchTask &t, const uint8_t *nonce, size_t nonce_len, uint32_t ntz, uint32_t worker_byte,
+                     uint32_t worker_bits) {
     memset(&t, 0, sizeof t);
     for (int w = 0; w < 4; ++w) t.iv[w] = kMd5IV[w];
     uint32_t M[16];
@@ -52,6 +50,8 @@ void fill_task(BatchTask &t, const uint8_t *nonce, size_t nonce_len, uint32_t nt
     t.len_bits = 8u * (uint32_t)(nonce_len + 1);
     t.dmask = tail_nibble_mask(ntz < 8u ? ntz : 8u);
 }
+
+namespace {
 
 // A live task of the round loop.
 struct Live {
@@ -125,17 +125,18 @@ int batch_state(BatchState **state, hipStream_t stream) {
     return 0;
 }
 
+}  // namespace
+
 // Wait for the completion record of launch `seq`: spin at first (a small round's record is a
 // few microseconds away), then sleep between polls; the stream is queried now and then so a
 // failed launch ends the wait with an error.
-int wait_record(const BatchRecord *rec, uint32_t seq, hipStream_t stream) {
+int batch_wait_record(const BatchRecord *rec, uint32_t seq, hipStream_t stream, const char *idle_msg) {
     const int64_t t0 = now_ns();
     for (uint64_t it = 1;; ++it) {
         if (__atomic_load_n(&rec->seq, __ATOMIC_ACQUIRE) == seq) return 0;
         const bool spinning = now_ns() - t0 < 200000;
         if (spinning ? (it % 4096 == 0) : (it % 16 == 0)) {
-            const int alive = stream_liveness(stream, &rec->seq, seq,
-                                              "dpow_search_batch: stream idle without the launch's completion record");
+            const int alive = stream_liveness(stream, &rec->seq, seq, idle_msg);
             if (alive != 0) return alive < 0 ? alive : 0;
         }
         if (spinning) {
@@ -147,16 +148,15 @@ int wait_record(const BatchRecord *rec, uint32_t seq, hipStream_t stream) {
     }
 }
 
-int check_task(const dpow_batch_task &t) {
-    if (t.nonce_len && !t.nonce) return set_error(DPOW_EINVAL, "dpow_search_batch: nonce is NULL");
-    if (t.nonce_len > DPOW_MAX_NONCE) return set_error(DPOW_EINVAL, "dpow_search_batch: nonce longer than DPOW_MAX_NONCE");
-    if (t.worker_byte > 255u) return set_error(DPOW_EINVAL, "dpow_search_batch: worker_byte > 255");
-    if (t.k_begin > t.k_end) return set_error(DPOW_EINVAL, "dpow_search_batch: k_begin > k_end");
-    if (t.k_end > DPOW_K_LIMIT) return set_error(DPOW_ERANGE, "dpow_search_batch: k_end beyond DPOW_K_LIMIT");
+int batch_check_task(const dpow_batch_task &t, const char *who) {
+    const std::string w(who);
+    if (t.nonce_len && !t.nonce) return set_error(DPOW_EINVAL, w + ": nonce is NULL");
+    if (t.nonce_len > DPOW_MAX_NONCE) return set_error(DPOW_EINVAL, w + ": nonce longer than DPOW_MAX_NONCE");
+    if (t.worker_byte > 255u) return set_error(DPOW_EINVAL, w + ": worker_byte > 255");
+    if (t.k_begin > t.k_end) return set_error(DPOW_EINVAL, w + ": k_begin > k_end");
+    if (t.k_end > DPOW_K_LIMIT) return set_error(DPOW_ERANGE, w + ": k_end beyond DPOW_K_LIMIT");
     return 0;
 }
-
-}  // namespace
 
 void batch_free(BatchState *s) {
     if (!s) return;
@@ -170,7 +170,7 @@ int batch_check(const dpow_batch_task *tasks, size_t n_tasks) {
     if (n_tasks == 0 || n_tasks > DPOW_BATCH_MAX)
         return set_error(DPOW_EINVAL, "dpow_search_batch: n_tasks must be in [1, DPOW_BATCH_MAX]");
     for (size_t i = 0; i < n_tasks; ++i) {
-        const int rc = check_task(tasks[i]);
+        const int rc = batch_check_task(tasks[i], "dpow_search_batch");
         if (rc < 0) return rc;
     }
     return 0;
@@ -210,7 +210,7 @@ int batch_run(BatchState **state, hipStream_t stream, const volatile uint32_t *c
     live.reserve(n);
     for (size_t i = 0; i < n; ++i) {
         const dpow_batch_task &t = tasks[i];
-        fill_task(img_tasks[i], t.nonce, t.nonce_len, t.ntz, t.worker_byte, t.worker_bits);
+        batch_fill_task(img_tasks[i], t.nonce, t.nonce_len, t.ntz, t.worker_byte, t.worker_bits);
         img_best[i] = t.best_global_idx;
         const uint32_t rbits = img_tasks[i].rbits;
         if (t.k_begin >= t.k_end || (t.k_begin << 8) >= t.best_global_idx) {
@@ -248,7 +248,9 @@ int batch_run(BatchState **state, hipStream_t stream, const volatile uint32_t *c
         const hipError_t e = batch_launch(reinterpret_cast<const BatchTask *>(s->d_mem),
                                           reinterpret_cast<const BatchEntry *>(s->d_h_mem + kMapOff), L, stream);
         if (e != hipSuccess) return hip_fail(e, "dpow_search_batch: launch");
-        if ((rc = wait_record(h_rec, L.seq, stream)) < 0) return rc;
+        if ((rc = batch_wait_record(h_rec, L.seq, stream,
+                                    "dpow_search_batch: stream idle without the launch's completion record")) < 0)
+            return rc;
         st.launches++;
         st.rounds++;
         if (h_rec->t_start != 0ull && h_rec->t_end >= h_rec->t_start)
@@ -298,7 +300,7 @@ int dpow_batch_candidate(const uint8_t *nonce, size_t nonce_len, uint32_t worker
     if ((local_idx >> remainder_bits(worker_bits)) >= DPOW_K_LIMIT)
         return set_error(DPOW_ERANGE, "dpow_batch_candidate: k beyond DPOW_K_LIMIT");
     BatchTask t;
-    fill_task(t, nonce, nonce_len, 0, worker_byte, worker_bits);
+    batch_fill_task(t, nonce, nonce_len, 0, worker_byte, worker_bits);
     for (int w = 0; w < 4; ++w) iv_out[w] = t.iv[w];
     *nblk_out = batch_candidate_words(t.T, t.p, t.rbits, t.base_tb, t.len_bits, local_idx, words_out);
     return 0;

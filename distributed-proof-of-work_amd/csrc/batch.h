@@ -25,6 +25,20 @@ struct BatchRound {
 // The round's shape for n_live tasks whose longest remaining range is max_left local indices.
 BatchRound batch_round(uint32_t round, size_t n_live, uint64_t max_left);
 
+uint64_t pow2_floor(uint64_t x);  // 0 for 0
+uint64_t pow2_ceil(uint64_t x);
+
+// What the task queue (queue.cpp) shares with the batch's host loop: a task's table row, the
+// argument errors of one task (`who`: the entry point named in the message), and the wait for a
+// launch's completion record (the stream-liveness check included; `idle_msg`: the error text when
+// the stream went idle without the record).
+struct BatchTask;
+struct BatchRecord;
+void batch_fill_task(BatchTask &t, const uint8_t *nonce, size_t nonce_len, uint32_t ntz, uint32_t worker_byte,
+                     uint32_t worker_bits);
+int batch_check_task(const dpow_batch_task &t, const char *who);
+int batch_wait_record(const BatchRecord *rec, uint32_t seq, hipStream_t stream, const char *idle_msg);
+
 // Device and pinned buffers of a context's batches: allocated on its first batch, freed with it.
 struct BatchState;
 void batch_free(BatchState *s);  // the context's device is current, its stream drained

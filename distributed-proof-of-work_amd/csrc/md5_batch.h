@@ -1,5 +1,6 @@
 // md5_batch.h -- the batched search (dpow_search_batch): definitions shared by the generic
-// gfx950 kernel (md5_batch.hip) and its host loop and planner (batch.cpp).
+// gfx950 kernel (md5_batch.hip) and its host loop and planner (batch.cpp), and by the task queue
+// that launches the same kernel code one descriptor per workgroup (queue.cpp).
 //
 // One kernel hashes B independent tasks over one grid.  Unlike the specialised kernels of
 // md5_search_kernel.h, whose message layout (NBLK, W0, SH) is a template parameter, a batch mixes
@@ -8,6 +9,8 @@
 // candidate assembles threadByte || chunk_k || 0x80 at byte p itself (batch_candidate_words, the
 // one piece of code behind both the kernel and dpow_batch_candidate).
 #pragma once
+
+#include <stddef.h>
 
 #include "dpow_common.h"
 
@@ -57,6 +60,20 @@ struct BatchLaunch {
     uint32_t n_blocks;             // rows * n_live
     uint32_t seq;
 };
+
+// The task queue (queue.cpp) launches queue_kernel over the same table: there a BatchEntry is one
+// workgroup's descriptor -- [i_begin, i_end) is the workgroup's own range, at most kBatchMaxGroup
+// local indices, and `task` the table slot -- and BatchLaunch::n_live counts the launch's live-slot
+// list (out_best[q] = best of slot out_slots[q]); BatchLaunch::group is unused.
+
+// One newly filled slot of the queue's task table, in pinned memory (queue_upload).
+struct QueueRow {
+    BatchTask t;
+    unsigned long long best;  // the task's bound
+    uint32_t slot;
+    uint32_t pad_;
+};
+static_assert(sizeof(QueueRow) == 144 && offsetof(QueueRow, best) == sizeof(BatchTask), "the best follows the row");
 
 // Chunk length of k (nextChunk^k, worker.go:234-244): the minimal little-endian bytes of k.
 DPOW_HD uint32_t batch_chunk_len(uint64_t k) {
@@ -192,6 +209,13 @@ hipError_t batch_launch(const BatchTask *tasks, const BatchEntry *map, const Bat
 // kernel on the batch's stream: a stream-ordered hipMemcpyAsync in front of the first launch cost
 // every batch ~0.2 ms.
 hipError_t batch_upload(uint32_t *dst, const uint32_t *src, uint32_t n_words, hipStream_t stream);
+// The task queue's kernels: the rows of newly filled slots to the table (n_rows may be 0), and one
+// launch of L.n_blocks descriptors with the live-slot list out_slots[0..L.n_live).
+hipError_t queue_prepare();
+hipError_t queue_upload(BatchTask *tasks, unsigned long long *best, const QueueRow *rows, uint32_t n_rows,
+                        hipStream_t stream);
+hipError_t queue_launch(const BatchTask *tasks, const BatchEntry *blocks, const uint32_t *out_slots,
+                        const BatchLaunch &L, hipStream_t stream);
 #endif
 
 }  // namespace dpow

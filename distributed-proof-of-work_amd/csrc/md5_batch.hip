@@ -1,4 +1,5 @@
-// md5_batch.hip -- the generic kernel of the batched search (dpow_search_batch, batch.cpp).
+// md5_batch.hip -- the generic kernel of the batched search (dpow_search_batch, batch.cpp) and,
+// further down, its second entry point for the task queue (queue_kernel, queue.cpp).
 //
 // One launch hashes a slice of every live task's window.  Workgroup b takes row b / n_live of
 // live entry b % n_live (chunk-major: a task's early indices are dispatched first), one candidate
@@ -132,6 +133,70 @@ __global__ void __launch_bounds__(kBlockThreads)
     for (uint32_t w = blockIdx.x * blockDim.x + threadIdx.x; w < n_words; w += gridDim.x * blockDim.x) dst[w] = src[w];
 }
 
+// The task queue's launch (queue.cpp): one descriptor per workgroup.  The live tasks of a queue
+// have different ages, so their slices differ by orders of magnitude and a (row, entry) grid would
+// be mostly empty; here workgroup b hashes [i_begin, i_end) (at most kBatchMaxGroup local indices)
+// of the task in table slot blocks[b].task, through the same BatchGroup as batch_kernel.  The
+// descriptors are read with one scalar load per workgroup: from pinned memory where the table is
+// short, as batch_kernel reads its map, else from the device copy the upload kernel made
+// (queue.h kQueueCopyBlocks).  Retirement as in batch_kernel; the last workgroup copies out the best values of
+// the launch's live-slot list out_slots[0..L.n_live), which is not the block list.
+__global__ void __launch_bounds__(kBlockThreads)
+    queue_kernel(const BatchTask *__restrict__ tasks, const BatchEntry *__restrict__ blocks,
+                 const uint32_t *__restrict__ out_slots, const BatchLaunch L) {
+    __shared__ uint32_t s_last;
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        __hip_atomic_store(L.t0, __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const BatchEntry *const e = blocks + blockIdx.x;
+    const uint64_t lo = e->i_begin, hi = e->i_end;
+    if (lo < hi) {
+        const uint32_t ti = e->task;
+        const BatchGroup g{tasks + ti, L.best + ti, lo, hi};
+        batch_with_w0(__builtin_amdgcn_readfirstlane(g.t->p >> 2), g);
+    }
+    // (see batch_kernel: every hit's atomicMin has returned, the barrier covers the four waves)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint32_t prev = __hip_atomic_fetch_add(L.done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        s_last = prev + 1u == L.n_blocks ? 1u : 0u;
+    }
+    __syncthreads();
+    if (s_last != 0u && threadIdx.x < 64u) {
+        for (uint32_t q = threadIdx.x; q < L.n_live; q += 64u) {
+            const unsigned long long b =
+                __hip_atomic_load(L.best + out_slots[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(L.out_best + q, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");  // the wave's stores before its lane 0's record
+        if (threadIdx.x == 0) {
+            __hip_atomic_store(L.done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const unsigned long long t_start = __hip_atomic_load(L.t0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&L.rec->t_start, t_start, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(&L.rec->t_end, __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(&L.rec->seq, L.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+}
+
+// The rows of the task table that changed since the queue's last launch (newly filled slots), from
+// pinned host memory to their slots: the task row and the slot's best.  In stream order before the
+// launch that reads them and after the launch that last used the slot.
+__global__ void __launch_bounds__(kBlockThreads)
+    queue_upload_kernel(uint32_t *__restrict__ tasks, uint32_t *__restrict__ best, const QueueRow *__restrict__ rows,
+                        uint32_t n_rows) {
+    constexpr uint32_t kTaskWords = sizeof(BatchTask) / 4, kWords = kTaskWords + 2;
+    const uint32_t n = n_rows * kWords;
+    for (uint32_t w = blockIdx.x * blockDim.x + threadIdx.x; w < n; w += gridDim.x * blockDim.x) {
+        const uint32_t r = w / kWords, c = w - r * kWords;
+        const uint32_t slot = rows[r].slot;
+        const uint32_t v = reinterpret_cast<const uint32_t *>(rows + r)[c];  // the best follows the task row
+        if (c < kTaskWords) tasks[slot * kTaskWords + c] = v;
+        else best[slot * 2u + (c - kTaskWords)] = v;
+    }
+}
+
 }  // namespace
 
 hipError_t batch_prepare() {
@@ -139,6 +204,29 @@ hipError_t batch_prepare() {
     hipError_t e = hipFuncGetAttributes(&a, reinterpret_cast<const void *>(batch_kernel));
     if (e == hipSuccess) e = hipFuncGetAttributes(&a, reinterpret_cast<const void *>(batch_upload_kernel));
     return e;
+}
+
+hipError_t queue_prepare() {
+    hipFuncAttributes a;
+    hipError_t e = hipFuncGetAttributes(&a, reinterpret_cast<const void *>(queue_kernel));
+    if (e == hipSuccess) e = hipFuncGetAttributes(&a, reinterpret_cast<const void *>(queue_upload_kernel));
+    return e;
+}
+
+hipError_t queue_upload(BatchTask *tasks, unsigned long long *best, const QueueRow *rows, uint32_t n_rows,
+                        hipStream_t stream) {
+    if (n_rows == 0u) return hipSuccess;
+    const uint32_t words = n_rows * (uint32_t)(sizeof(BatchTask) / 4 + 2);
+    const uint32_t blocks = (words + kBlockThreads - 1u) / kBlockThreads;
+    hipLaunchKernelGGL(queue_upload_kernel, dim3(blocks), dim3(kBlockThreads), 0, stream,
+                       reinterpret_cast<uint32_t *>(tasks), reinterpret_cast<uint32_t *>(best), rows, n_rows);
+    return hipGetLastError();
+}
+
+hipError_t queue_launch(const BatchTask *tasks, const BatchEntry *blocks, const uint32_t *out_slots,
+                        const BatchLaunch &L, hipStream_t stream) {
+    hipLaunchKernelGGL(queue_kernel, dim3(L.n_blocks), dim3(kBlockThreads), 0, stream, tasks, blocks, out_slots, L);
+    return hipGetLastError();
 }
 
 hipError_t batch_upload(uint32_t *dst, const uint32_t *src, uint32_t n_words, hipStream_t stream) {

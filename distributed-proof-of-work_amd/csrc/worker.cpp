@@ -10,6 +10,11 @@
 // A task's cancel channel (cap 1, worker.go:172) becomes a kill counter plus
 // the pinned cancel flag of the dpow_ctx its miner searches with, so a
 // Found/Cancel stops the kernel mid-launch instead of at the next candidate.
+//
+// Queue mode (dpow_worker_set_queue, off by default): the first window of a task that does not
+// go to the board, k in [0, 2^16), is a task of the worker's one dpow_queue instead of a search
+// on a context of its own, so concurrent small Mines share launches; a kill then also cancels the
+// task's ticket.  A first window that is exhausted continues on a context as before.
 #include <stdio.h>
 #include <string.h>
 
@@ -80,6 +85,8 @@ struct Task {
     std::condition_variable cv;
     int kills = 0;              // messages sent on the cap-1 cancel channel
     dpow_ctx *ctx = nullptr;    // set while the miner searches
+    dpow_queue *q = nullptr;    // queue mode: set, with the ticket, while the first window is queued
+    uint64_t q_ticket = 0;
 };
 
 struct CacheEntry {
@@ -92,6 +99,8 @@ struct CacheEntry {
 struct dpow_worker {
     int device = 0;
     std::atomic<dpow_board *> board{nullptr};                // node mode (dpow_worker_set_board)
+    std::atomic<dpow_queue *> queue{nullptr};                // queue mode (dpow_worker_set_queue)
+    dpow_queue *queue_owned = nullptr;                       // opened by the first dpow_worker_set_queue(w, 1)
     std::mutex tasks_mu;                                    // WorkerMineTasks.mu
     std::map<std::string, std::shared_ptr<Task>> tasks;     // WorkerMineTasks.tasks
     std::mutex cache_mu;                                    // WorkerResultCache.mu
@@ -205,6 +214,7 @@ struct dpow_worker {
         std::lock_guard<std::mutex> g(t.m);
         t.kills++;
         if (t.ctx) *dpow_cancel_flag(t.ctx) = 1u;
+        if (t.q_ticket) (void)dpow_queue_cancel(t.q, t.q_ticket);
         t.cv.notify_all();
     }
     static void wait_kill(Task &t) {  // <-killChan
@@ -245,16 +255,49 @@ struct dpow_worker {
             send(t.nonce, t.ntz, wb, nullptr, t.token);
             return;
         }
-        dpow_ctx *ctx = acquire_ctx();
+        int status = DPOW_EXHAUSTED;
+        bool own_hit = true;
+        dpow_board *const nb = board.load();
+        const bool node = nb && t.wbits >= 1 && t.wbits <= 6 && t.wb < (1u << t.wbits);
+        uint64_t k = 0, window = 1ull << 16;
+        dpow_queue *const q = node ? nullptr : queue.load();
+        if (q) {
+            // The first window as a task of the worker's queue.  DPOW_EAGAIN (DPOW_BATCH_MAX Mines
+            // undecided) leaves the window to a context, like any other.
+            uint64_t ticket = 0;
+            int rc = dpow_queue_submit(q, t.nonce.data(), t.nonce.size(), t.ntz, t.wb, t.wbits, 0, window, DPOW_NO_HIT,
+                                       t.token, &ticket);
+            if (rc == 0) {
+                bool killed;
+                {
+                    std::lock_guard<std::mutex> g(t.m);
+                    t.q = q;
+                    t.q_ticket = ticket;
+                    killed = t.kills > 0;
+                }
+                if (killed) (void)dpow_queue_cancel(q, ticket);
+                dpow_queue_result r;
+                rc = dpow_queue_wait(q, ticket, &r, -1);
+                {
+                    std::lock_guard<std::mutex> g(t.m);
+                    t.q = nullptr;
+                    t.q_ticket = 0;
+                }
+                status = rc == 1 ? r.status : rc < 0 ? rc : DPOW_EHIP;
+                if (status == DPOW_FOUND) secret.assign(r.secret, r.secret + r.secret_len);
+                k = window;
+                window <<= 4;
+            } else if (rc != DPOW_EAGAIN) {
+                status = rc;
+            }
+        }
+        const bool need_ctx = status == DPOW_EXHAUSTED;  // always, unless the queue decided the task
+        dpow_ctx *ctx = need_ctx ? acquire_ctx() : nullptr;
         if (ctx) {
             std::lock_guard<std::mutex> g(t.m);
             t.ctx = ctx;
             if (t.kills > 0) *dpow_cancel_flag(ctx) = 1u;
         }
-        int status = DPOW_EXHAUSTED;
-        bool own_hit = true;
-        dpow_board *const nb = board.load();
-        const bool node = nb && t.wbits >= 1 && t.wbits <= 6 && t.wb < (1u << t.wbits);
         if (ctx && node) {
             // The node's search of this task (dpow.h dpow_board_search): the deterministic first
             // hit of all W partitions; reported by its owner only.
@@ -269,7 +312,6 @@ struct dpow_worker {
                 own_hit = owner != 0;
             }
         }
-        uint64_t k = 0, window = 1ull << 16;
         while (ctx && !node && status == DPOW_EXHAUSTED && k < DPOW_K_LIMIT) {  // worker.go:318-400
             const uint64_t ke = k + window < DPOW_K_LIMIT ? k + window : DPOW_K_LIMIT;
             uint64_t best = DPOW_NO_HIT;
@@ -286,12 +328,12 @@ struct dpow_worker {
             t.ctx = nullptr;
         }
         if (ctx) release_ctx(ctx);
-        if (status < 0 || !ctx) {
+        if (status < 0 || (need_ctx && !ctx)) {
             // The GPU search failed (no device, a HIP error, a hit that failed host
             // verification).  The Go miner cannot fail here; waiting for a kill
             // would hang the coordinator until its timeout.  Report the error on
             // the result channel and end the task.
-            const int32_t code = ctx ? status : DPOW_EHIP;
+            const int32_t code = status < 0 ? status : DPOW_EHIP;
             const std::string err = dpow_last_error();
             record(t.token, "MinerError", fields(t.nonce, t.ntz, nullptr, &wb) + ",\"Code\":" +
                                               std::to_string(code) + ",\"Error\":\"" + json_escape(err) + "\"");
@@ -352,12 +394,23 @@ void dpow_worker_free(dpow_worker *w) {
     }
     for (auto &th : w->threads) th.join();
     for (dpow_ctx *c : w->pool) dpow_close(c);
+    dpow_queue_close(w->queue_owned);
     delete w;
 }
 
 int dpow_worker_set_board(dpow_worker *w, dpow_board *b) {
     if (!w) return DPOW_EINVAL;
     w->board.store(b);
+    return 0;
+}
+
+int dpow_worker_set_queue(dpow_worker *w, int on) {
+    if (!w) return DPOW_EINVAL;
+    if (on && !w->queue_owned) {
+        const int rc = dpow_queue_open(w->device, &w->queue_owned);
+        if (rc < 0) return rc;
+    }
+    w->queue.store(on ? w->queue_owned : nullptr);
     return 0;
 }
 

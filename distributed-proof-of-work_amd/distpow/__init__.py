@@ -3,13 +3,14 @@
 The worker's brute-force search (worker.go:258-401) runs as a hand-written gfx950
 HIP kernel in libdpow.so; this package is the host side above its C ABI.
 """
-from ._lib import (CANCELLED, DPOW_K_LIMIT, DPOW_MAX_SECRET, DPOW_NO_HIT, EHIP, EINVAL, EPROTO, ERANGE,
+from ._lib import (CANCELLED, DPOW_K_LIMIT, DPOW_MAX_SECRET, DPOW_NO_HIT, EAGAIN, EHIP, EINVAL, EPROTO, ERANGE,
                    EVERIFY, EXHAUSTED, FOUND, LIB_PATH, DpowError, build_id, lib)
-from .search import (BatchTask, Miner, SearchResult, batch_candidate, batch_plan, batch_plan_block, device_count,
-                     global_index, md5, plan_candidate, plan_window,
+from .search import (BatchTask, Miner, QueueResult, SearchResult, TaskQueue, batch_candidate, batch_plan, batch_plan_block, device_count,
+                     global_index, md5, plan_candidate, plan_window, queue_plan,
                      remainder_bits, secret_from_index, thread_bytes, trailing_zero_nibbles, verify)
 
 __all__ = ["Miner", "SearchResult", "BatchTask", "batch_candidate", "batch_plan", "batch_plan_block",
+           "TaskQueue", "QueueResult", "queue_plan", "EAGAIN",
            "DpowError", "lib", "LIB_PATH", "device_count", "md5", "verify",
            "secret_from_index", "trailing_zero_nibbles", "thread_bytes", "remainder_bits", "global_index",
            "plan_window", "plan_candidate", "DPOW_NO_HIT", "DPOW_K_LIMIT", "DPOW_MAX_SECRET", "FOUND",

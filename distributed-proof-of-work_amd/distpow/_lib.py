@@ -46,6 +46,7 @@ class PlanLaunch(ctypes.Structure):
 
 DPOW_MAX_NONCE = 1024
 EPROTO, ETIMEOUT = -6, -7
+EAGAIN = -8  # dpow_queue_submit: DPOW_BATCH_MAX tasks undecided
 
 
 class LaunchTime(ctypes.Structure):
@@ -90,6 +91,14 @@ class BatchRange(ctypes.Structure):
     """dpow_batch_range (include/dpow.h)."""
     _fields_ = [("launch", ctypes.c_uint32), ("task", ctypes.c_uint32), ("i_begin", ctypes.c_uint64),
                 ("i_end", ctypes.c_uint64), ("group", ctypes.c_uint32), ("rows", ctypes.c_uint32)]
+
+
+class QueueResultC(ctypes.Structure):
+    """dpow_queue_result (include/dpow.h)."""
+    _fields_ = [("ticket", ctypes.c_uint64), ("user", ctypes.c_uint64), ("status", ctypes.c_int32),
+                ("secret_len", ctypes.c_uint32), ("global_idx", ctypes.c_uint64),
+                ("secret", ctypes.c_uint8 * DPOW_MAX_SECRET), ("launches", ctypes.c_uint32),
+                ("pad", ctypes.c_uint32), ("queued_ms", ctypes.c_double)]
 
 
 _lib = None
@@ -257,6 +266,17 @@ def lib():
                                            ctypes.c_size_t, u64p]),
         "dpow_batch_plan_block": (ctypes.c_int, [ctypes.POINTER(BatchRange), ctypes.c_uint32, ctypes.c_uint32,
                                                  u32p, u64p, u64p]),
+        "dpow_queue_open": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(vp)]),
+        "dpow_queue_close": (None, [vp]),
+        "dpow_queue_submit": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32,
+                                             ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
+                                             ctypes.c_uint64, u64p]),
+        "dpow_queue_cancel": (ctypes.c_int, [vp, ctypes.c_uint64]),
+        "dpow_queue_next": (ctypes.c_int, [vp, ctypes.POINTER(QueueResultC), ctypes.c_int]),
+        "dpow_queue_wait": (ctypes.c_int, [vp, ctypes.c_uint64, ctypes.POINTER(QueueResultC), ctypes.c_int]),
+        "dpow_queue_stats": (ctypes.c_int, [vp, ctypes.POINTER(BatchStats), u32p, u32p]),
+        "dpow_queue_plan": (ctypes.c_int, [u64p, u32p, ctypes.c_size_t, ctypes.POINTER(BatchRange),
+                                           ctypes.c_size_t, u64p]),
         "dpow_get_stats": (ctypes.c_int, [vp, ctypes.POINTER(Stats)]),
         "dpow_reset_stats": (None, [vp]),
         "dpow_stream": (vp, [vp]),
@@ -291,6 +311,7 @@ def lib():
         "dpow_worker_trace": (ctypes.c_size_t, [vp, ctypes.c_char_p, ctypes.c_size_t]),
         "dpow_worker_active_tasks": (ctypes.c_int, [vp]),
         "dpow_worker_set_board": (ctypes.c_int, [vp, vp]),
+        "dpow_worker_set_queue": (ctypes.c_int, [vp, ctypes.c_int]),
     }
     missing = [name for name in sig if not hasattr(L, name)]
     if missing:  # same ABI version, yet entry points missing: not a library of this ABI either

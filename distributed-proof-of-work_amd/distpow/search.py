@@ -15,6 +15,7 @@ from ._lib import (CANCELLED, DPOW_K_LIMIT, DPOW_MAX_SECRET, DPOW_NO_HIT, EXHAUS
                    PlanLaunch, Stats, check, lib)
 
 __all__ = ["Miner", "SearchResult", "BatchTask", "batch_candidate", "batch_plan", "batch_plan_block",
+           "TaskQueue", "QueueResult", "queue_plan",
            "secret_from_index", "md5", "verify", "trailing_zero_nibbles",
            "thread_bytes", "remainder_bits", "global_index", "plan_window", "plan_candidate",
            "device_count", "DPOW_NO_HIT", "FOUND", "EXHAUSTED", "CANCELLED"]
@@ -141,6 +142,106 @@ def batch_plan_block(entries, n_live, block):
     r = check(lib().dpow_batch_plan_block(entries, n_live, block, ctypes.byref(task), ctypes.byref(lo),
                                           ctypes.byref(hi)), "dpow_batch_plan_block")
     return (task.value, lo.value, hi.value) if r else None
+
+
+def queue_plan(left: Sequence[int], age: Sequence[int]):
+    """One launch of the task queue for live tasks with left[i] local indices to go and age[i]
+    launches behind them (dpow_queue_plan): (blocks, budget), blocks a ctypes array of BatchRange,
+    one per workgroup in descriptor order, ranges relative to each task's current position."""
+    n = len(left)
+    if len(age) != n:
+        raise ValueError("queue_plan: left and age differ in length")
+    la = (ctypes.c_uint64 * max(n, 1))(*left)
+    aa = (ctypes.c_uint32 * max(n, 1))(*age)
+    budget = ctypes.c_uint64()
+    cnt = check(lib().dpow_queue_plan(la, aa, n, None, 0, ctypes.byref(budget)), "dpow_queue_plan")
+    arr = (_lib.BatchRange * max(cnt, 1))()
+    check(lib().dpow_queue_plan(la, aa, n, arr, cnt, ctypes.byref(budget)), "dpow_queue_plan")
+    return (_lib.BatchRange * cnt).from_buffer(arr), budget.value
+
+
+@dataclass
+class QueueResult:
+    """One decided task of a TaskQueue (dpow_queue_result)."""
+    result: SearchResult
+    ticket: int
+    user: int = 0
+    launches: int = 0        # launches the task took part in
+    queued_ms: float = 0.0   # submit to decided, on the host clock
+
+    @property
+    def status(self):
+        return self.result.status
+
+
+class TaskQueue:
+    """The batched search as a service on one GPU (dpow_queue_*): tasks are submitted, cancelled and
+    collected one by one, from any thread, while the queue's launches keep running over whatever
+    is live.  A task's answer is what Miner.search returns for it."""
+
+    def __init__(self, device: int = 0):
+        self._q = ctypes.c_void_p()
+        check(lib().dpow_queue_open(device, ctypes.byref(self._q)), "dpow_queue_open")
+        self.device = device
+
+    def close(self):
+        """Cancels what is undecided and ends the queue (no other call may be in flight)."""
+        if self._q:
+            lib().dpow_queue_close(self._q)
+            self._q = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def submit(self, task: BatchTask, user: int = 0) -> int:
+        """Queue one task; returns its ticket.  DpowError with code EAGAIN when DPOW_BATCH_MAX tasks
+        are undecided."""
+        n = _b(task.nonce)
+        ticket = ctypes.c_uint64()
+        check(lib().dpow_queue_submit(self._q, n, len(n), task.num_trailing_zeros, task.worker_byte,
+                                      task.worker_bits, task.k_begin, task.k_end, task.bound, user,
+                                      ctypes.byref(ticket)), "dpow_queue_submit")
+        return ticket.value
+
+    def cancel(self, ticket: int) -> bool:
+        """True when the task was undecided and is CANCELLED now; False when it was decided already."""
+        return check(lib().dpow_queue_cancel(self._q, ticket), "dpow_queue_cancel") == 1
+
+    @staticmethod
+    def _result(c) -> QueueResult:
+        res = (SearchResult(FOUND, c.global_idx, bytes(c.secret[:c.secret_len])) if c.status == FOUND
+               else SearchResult(c.status))
+        return QueueResult(res, c.ticket, c.user, c.launches, c.queued_ms)
+
+    def next(self, timeout_ms: int = -1) -> Optional[QueueResult]:
+        """Any decided task, in the order they were decided; None on time-out (timeout_ms < 0 blocks).
+        A task the queue's failure ended carries the negative code as its status."""
+        c = _lib.QueueResultC()
+        r = check(lib().dpow_queue_next(self._q, ctypes.byref(c), timeout_ms), "dpow_queue_next")
+        return self._result(c) if r else None
+
+    def wait(self, ticket: int, timeout_ms: int = -1) -> Optional[QueueResult]:
+        """The given task's result; None on time-out.  Each result is handed out once, by next or wait."""
+        c = _lib.QueueResultC()
+        r = check(lib().dpow_queue_wait(self._q, ticket, ctypes.byref(c), timeout_ms), "dpow_queue_wait")
+        return self._result(c) if r else None
+
+    def stats(self):
+        """(BatchStats totals since open, tasks undecided, results not yet collected)."""
+        st = _lib.BatchStats()
+        live, unc = ctypes.c_uint32(), ctypes.c_uint32()
+        check(lib().dpow_queue_stats(self._q, ctypes.byref(st), ctypes.byref(live), ctypes.byref(unc)),
+              "dpow_queue_stats")
+        return st, live.value, unc.value
 
 
 def device_count() -> int:

@@ -77,10 +77,21 @@ class Board:
 
 
 class Worker:
-    def __init__(self, device: int = 0):
+    def __init__(self, device: int = 0, queue: bool = False):
         self._w = ctypes.c_void_p()
         check(lib().dpow_worker_new(device, ctypes.byref(self._w)), "dpow_worker_new")
         self.device = device
+        if queue:
+            try:
+                self.set_queue(True)
+            except Exception:
+                self.close()
+                raise
+
+    def set_queue(self, on: bool):
+        """Queue mode (dpow_worker_set_queue): the first window of each Mine is a task of the worker's
+        one task queue, so concurrent small Mines share launches.  Before the first Mine."""
+        check(lib().dpow_worker_set_queue(self._w, 1 if on else 0), "dpow_worker_set_queue")
 
     def set_board(self, board: Optional[Board]):
         """Node mode (dpow_worker_set_board): tasks with 1 <= workerBits <= 6 search on the board."""

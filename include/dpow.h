@@ -34,6 +34,7 @@ extern "C" {
  * The batch entry points (dpow_search_batch, dpow_batch_candidate, dpow_batch_plan,
  * dpow_batch_plan_block) were added within ABI 5: nothing older changed, and the Python binding
  * refuses a library that lacks a prototype it lists, or one built from another tree.
+ * The task queue (dpow_queue_*, DPOW_EAGAIN) and dpow_worker_set_queue were added the same way.
  * A consumer built against another version must refuse the library before any
  * other call (distpow/_lib.py check_abi, tests/c/abi_harness.c). */
 #define DPOW_ABI_VERSION 5
@@ -158,6 +159,66 @@ typedef struct dpow_batch_stats {
     double kernel_ms;             /* sum of the launches' durations, as they stamp them */
 } dpow_batch_stats;
 int dpow_search_batch(dpow_ctx *ctx, dpow_batch_task *tasks, size_t n_tasks, dpow_batch_stats *stats);
+
+/* ---------------------------------------------------------------------------
+ * Task queue (added within ABI 5): the batched search as a service on one GPU.
+ *
+ * dpow_search_batch wants its tasks at once and returns when the slowest is decided; the
+ * reference's Mine requests arrive one at a time, each wants its answer as soon as it exists,
+ * and each is killed on its own (worker.go:169-232).  A queue takes tasks one by one from any
+ * thread while its pump thread keeps launching the generic kernel over whatever is live: a
+ * task is a dpow_search argument tuple and gets the answer dpow_search gives for it (the first
+ * hit below its bound in the reference's order, re-verified with the host MD5), as soon as the
+ * launch that decides it has retired.  One launch is in flight per queue and every launch is
+ * bounded; how a launch is shared among tasks of different ages is DESIGN.md section 12
+ * (dpow_queue_plan below).  An idle queue issues no GPU work and does not poll.
+ *
+ * A queue owns a private context on its device, DPOW_BATCH_MAX task slots and its pump thread.
+ * Every entry point may be called from any thread between open and close; close is called
+ * once, with no other call in flight.
+ * ------------------------------------------------------------------------- */
+#define DPOW_EAGAIN (-8)   /* dpow_queue_submit: DPOW_BATCH_MAX tickets are out; nothing queued */
+typedef struct dpow_queue dpow_queue;
+typedef struct dpow_queue_result {
+    uint64_t ticket, user;        /* ticket: never 0, never reused in a queue's life */
+    int32_t status;               /* DPOW_FOUND / EXHAUSTED / CANCELLED, or a negative code */
+    uint32_t secret_len;
+    uint64_t global_idx;          /* on DPOW_FOUND */
+    uint8_t secret[DPOW_MAX_SECRET];
+    uint32_t launches;            /* launches the task took part in */
+    uint32_t pad;
+    double queued_ms;             /* submit to decided, on the host clock */
+} dpow_queue_result;
+
+/* DPOW_EINVAL for out = NULL or a bad ordinal, DPOW_EHIP without a visible device (as dpow_open). */
+int dpow_queue_open(int device, dpow_queue **out);
+/* Cancels what is undecided, lets the launch in flight retire, joins the pump, closes the context. */
+void dpow_queue_close(dpow_queue *q);
+/* Queue one task (the nonce is copied) and return its ticket.  The argument errors of
+ * dpow_search_batch (DPOW_EINVAL, DPOW_ERANGE) are returned before any GPU work; DPOW_EAGAIN
+ * with DPOW_BATCH_MAX tickets out (tasks undecided, or decided and not yet collected: collecting
+ * one makes room); the queue's failure code once a launch has failed.  A
+ * window that is empty or starts at or above `bound` is DPOW_EXHAUSTED without a launch. */
+int dpow_queue_submit(dpow_queue *q, const uint8_t *nonce, size_t nonce_len, uint32_t ntz,
+                      uint32_t worker_byte, uint32_t worker_bits, uint64_t k_begin, uint64_t k_end,
+                      uint64_t bound, uint64_t user, uint64_t *ticket);
+/* 1: the task was undecided and is DPOW_CANCELLED now -- its result is available at once, before
+ * the launch in flight ends, and wins over a hit that launch may still find (worker.go:320-342);
+ * 0: it was decided already (its result stands) or the ticket is unknown. */
+int dpow_queue_cancel(dpow_queue *q, uint64_t ticket);
+/* Collect a result: dpow_queue_next any decided task, in the order they were decided;
+ * dpow_queue_wait the given one.  1 with *out filled, 0 on time-out (timeout_ms < 0 blocks), or a
+ * negative code (DPOW_EINVAL: a NULL argument, or a ticket that is neither undecided nor waiting to
+ * be collected; the queue's failure code when it has failed and nothing is left to collect).
+ * Each result is handed out exactly once, to whichever of the two asks first.  After a failed
+ * launch (a HIP error, DPOW_EVERIFY, a stream idle without its record) every undecided task's
+ * result carries that negative code as its status; nothing is retried. */
+int dpow_queue_next(dpow_queue *q, dpow_queue_result *out, int timeout_ms);
+int dpow_queue_wait(dpow_queue *q, uint64_t ticket, dpow_queue_result *out, int timeout_ms);
+/* Totals since open (launches = rounds; candidates of the launches' slices; kernel ms from the
+ * records' ticks), tasks undecided, results not yet collected.  Any pointer may be NULL. */
+int dpow_queue_stats(dpow_queue *q, dpow_batch_stats *out, uint32_t *live, uint32_t *uncollected);
+/* (dpow_queue_plan, the queue's launch planner, is with the host helpers below.) */
 
 /* ---------------------------------------------------------------------------
  * Node slot (round 3): the Found fan-out of one node's ranks, in shared memory.
@@ -373,6 +434,18 @@ int dpow_batch_plan(const uint64_t *k_begin, const uint64_t *k_end, const uint32
  * in an earlier row), or a negative error code. */
 int dpow_batch_plan_block(const dpow_batch_range *entries, uint32_t n_live, uint32_t block,
                           uint32_t *task, uint64_t *lo, uint64_t *hi);
+
+/* The task queue's planner for one launch (host logic of dpow_queue_*, exposed for testing;
+ * DESIGN.md section 12): live task i has left[i] > 0 local indices to go and has taken part in
+ * age[i] launches.  One entry per workgroup, in descriptor order (by the block's ordinal within
+ * its task, then by task): task = index into the inputs, [i_begin, i_end) relative to the task's
+ * current position, group = the launch's block size, rows = the task's block count, launch = 0.
+ * When every task has the same age the slices and the group are those of dpow_batch_plan's round
+ * of that age.  Returns the block count (may exceed max_blocks, in which case only the first
+ * max_blocks are written) or a negative code (DPOW_EINVAL: a NULL argument, n_tasks of 0 or above
+ * DPOW_BATCH_MAX, a left[i] of 0); *budget_out = the launch's candidate budget. */
+int dpow_queue_plan(const uint64_t *left, const uint32_t *age, size_t n_tasks,
+                    dpow_batch_range *out, size_t max_blocks, uint64_t *budget_out);
 
 /* ---------------------------------------------------------------------------
  * Introspection / measurement.

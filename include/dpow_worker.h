@@ -66,6 +66,15 @@ void dpow_worker_free(dpow_worker *w);
  * the board must outlive the worker's tasks.  Set it before the first Mine. */
 int dpow_worker_set_board(dpow_worker *w, dpow_board *b);
 
+/* Queue mode (added within ABI 5), off by default: with on != 0 the first window of every task
+ * that does not go to the board, k in [0, 2^16), is a task of the worker's one task queue (dpow.h
+ * dpow_queue_*) instead of a search on a context of its own, so concurrent small Mines share
+ * launches; a Found or Cancel also cancels the task's ticket.  A first window without a hit
+ * continues with dpow_search as before.  Messages, trace actions and the cache are unchanged.
+ * The first call with on != 0 opens the queue: its error code (DPOW_EHIP without a device) is
+ * returned and the mode stays off.  Set it before the first Mine. */
+int dpow_worker_set_queue(dpow_worker *w, int on);
+
 /* WorkerRPCHandler.Mine (worker.go:169-185): register the task (key
  * hex(nonce)|ntz|workerByte), record WorkerMine, start the miner thread. */
 int dpow_worker_mine(dpow_worker *w, const uint8_t *nonce, size_t nonce_len, uint32_t ntz,

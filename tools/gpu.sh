@@ -27,6 +27,8 @@
 #   node-ab runs name=lib.so[,VAR=value...] ...   the emulated 8-GPU node per library, then ab
 #   batch [reps]     the batched search's GPU tests, then its tasks-per-second table against the looped
 #                    and the 8-thread paths (tools/batch_rate.py -> batch_rate.json)
+#   queue [reps]     the task queue's GPU tests, then its rate and latency tables (tools/queue_rate.py ->
+#                    queue_rate.json)
 set -o pipefail
 task=${1:?task}; tag=${2:?tag}; shift 2
 out=gpurun_out/$tag
@@ -107,6 +109,11 @@ batch)
     timeout -k 10 300 python3 -u -m pytest tests/test_gpu_batch.py -m gpu -x -v -s > $out/pytest_batch.txt 2>&1 &&
     timeout -k 10 500 python3 -u tools/batch_rate.py --reps "${1:-5}" --out $out/batch_rate.json \
         > $out/batch_rate.txt 2> $out/batch_rate.err ;;
+queue)
+    timeout -k 10 300 python3 -u -m pytest tests/test_gpu_queue.py tests/test_gpu_worker_queue.py -m gpu -x -v -s \
+        > $out/pytest_queue.txt 2>&1 &&
+    timeout -k 10 400 python3 -u tools/queue_rate.py --reps "${1:-5}" --out $out/queue_rate.json \
+        > $out/queue_rate.txt 2> $out/queue_rate.err ;;
 ab) timeout -k 10 800 python3 -u tools/ab_variants.py "$@" > $out/ab.log 2>&1 ;;
 node-ab)
     runs=$1; shift

@@ -24,4 +24,5 @@ unit ls1_0 md5_variant.hip -DDPOW_VLS=1 -DDPOW_VNBLK=1 -DDPOW_VSH=0 "$@" &
 unit ls2_0 md5_variant.hip -DDPOW_VLS=1 -DDPOW_VNBLK=2 -DDPOW_VSH=0 "$@" &
 unit si1_0 md5_variant.hip -DDPOW_VSI=1 -DDPOW_VNBLK=1 -DDPOW_VSH=0 "$@" &
 unit ctrl search_ctrl.hip "$@" &
+unit batch md5_batch.hip "$@" &  # batch_kernel, queue_kernel and their upload kernels
 wait
