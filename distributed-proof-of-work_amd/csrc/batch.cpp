@@ -1,6 +1,6 @@
 // batch.cpp -- host side of the batched search: dpow_search_batch's round loop over the generic
-// kernel (md5_batch.hip), its round planner, and the host helpers dpow_batch_candidate /
-// dpow_batch_plan / dpow_batch_plan_block.
+// kernel (md5_batch.hip) on the launch engine (batch_engine.h), the round schedule and planner, and
+// the host helpers dpow_batch_candidate / dpow_batch_plan / dpow_batch_plan_block.
 //
 // Rounds.  Round r covers the next slice of every live (undecided) task's local index range,
 // the same slice for every task: kBatchFirst * 4^r candidates in all (capped at kBatchCap) split
@@ -10,18 +10,16 @@
 // flight at a time and every launch is bounded, so a return leaves nothing queued.
 #include <hip/hip_runtime.h>
 #include <string.h>
-#include <time.h>
 
 #include <algorithm>
-#include <string>
 #include <vector>
 
 #include "../../include/dpow.h"
 #include "../../include/dpow_worker.h"
 #include "batch.h"
+#include "batch_engine.h"
 #include "ctx.h"
 #include "md5_batch.h"
-#include "md5_host.h"
 #include "plan.h"
 
 namespace dpow {
@@ -29,34 +27,20 @@ namespace dpow {
 uint64_t pow2_floor(uint64_t x) { return x ? 1ull << (63 - __builtin_clzll(x)) : 0; }
 uint64_t pow2_ceil(uint64_t x) { return x <= 1 ? 1 : pow2_floor(x - 1) << 1; }
 
-// Midstate, final-block template and partition of one task.
-void batch_fill_task(BatchTask &t, const uint8_t *nonce, size_t nonce_len, uint32_t ntz, uint32_t worker_byte,
-                     uint32_t worker_bits) {
-    memset(&t, 0, sizeof t);
-    for (int w = 0; w < 4; ++w) t.iv[w] = kMd5IV[w];
-    uint32_t M[16];
-    size_t off = 0;
-    for (; off + 64 <= nonce_len; off += 64) {
-        for (int w = 0; w < 16; ++w) M[w] = load_le32(nonce + off + 4 * w);
-        md5_compress(t.iv, M);
-    }
-    uint8_t tail[64] = {0};
-    if (nonce_len > off) memcpy(tail, nonce + off, nonce_len - off);
-    for (int w = 0; w < 16; ++w) t.T[w] = load_le32(tail + 4 * w);
-    t.p = (uint32_t)(nonce_len - off);
-    t.rbits = remainder_bits(worker_bits);
-    t.base_tb = base_thread_byte(worker_byte, worker_bits);
-    t.ntz = ntz;
-    t.len_bits = 8u * (uint32_t)(nonce_len + 1);
-    t.dmask = tail_nibble_mask(ntz < 8u ? ntz : 8u);
+uint64_t batch_budget(uint32_t step) { return std::min(kBatchFirst << (2 * std::min<uint32_t>(step, 8u)), kBatchCap); }
+
+uint32_t batch_group(uint64_t total) {
+    return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(pow2_floor(total / kBatchBlocks), kBatchMinGroup),
+                                        kBatchMaxGroup);
 }
 
 namespace {
 
-// A live task of the round loop.
+// A live task of the round loop (its partition: what settling it needs, kept out of pinned memory).
 struct Live {
     uint32_t task;
     uint64_t i_cur, i_end;
+    uint32_t rbits, base_tb;
 };
 
 // The entries of one round for `live` (in order), and the round's shape.
@@ -78,90 +62,44 @@ BatchRound plan_round(uint32_t round, const std::vector<Live> &live, std::vector
 }  // namespace
 
 BatchRound batch_round(uint32_t round, size_t n_live, uint64_t max_left) {
-    const uint64_t target = std::min(kBatchFirst << (2 * std::min<uint32_t>(round, 8u)), kBatchCap);
-    uint64_t slice = std::max(pow2_floor(target / (uint64_t)std::max<size_t>(n_live, 1)), kBatchMinSlice);
+    uint64_t slice = std::max(pow2_floor(batch_budget(round) / (uint64_t)std::max<size_t>(n_live, 1)), kBatchMinSlice);
     slice = std::min(slice, pow2_ceil(max_left));  // no rows past the longest range left
-    const uint64_t total = slice * (uint64_t)n_live;
-    const uint64_t group = std::min<uint64_t>(std::max<uint64_t>(pow2_floor(total / kBatchBlocks), kBatchMinGroup),
-                                              kBatchMaxGroup);
     BatchRound r;
     r.slice = slice;
-    r.group = (uint32_t)group;
-    r.rows = (uint32_t)((slice + group - 1) / group);
+    r.group = batch_group(slice * (uint64_t)n_live);
+    r.rows = (uint32_t)((slice + r.group - 1) / r.group);
     return r;
 }
 
+// The context's buffers.  Device: the upload image [BatchTask x n][best x n] of the running batch,
+// the control words behind (batch_engine.h).  Pinned: the upload image, the launch map, out_best,
+// the record.
 struct BatchState {
-    char *d_mem = nullptr;     // device: [BatchTask x n][best x n] of the running batch, the control words behind
-    char *h_mem = nullptr;     // pinned, mapped: the upload image, the launch map, out_best, the record
-    char *d_h_mem = nullptr;   // device alias of h_mem
-    uint32_t seq = 0;
+    EngineBuffers buf;
 };
 
 namespace {
-constexpr size_t kImageBytes = DPOW_BATCH_MAX * (sizeof(BatchTask) + sizeof(unsigned long long));
-constexpr size_t kCtlOff = kImageBytes;                      // d_mem: done (u32) at +0, t0 (u64) at +8
-constexpr size_t kDevBytes = kImageBytes + 64;
-constexpr size_t kMapOff = kImageBytes;                      // h_mem
-constexpr size_t kOutOff = kMapOff + DPOW_BATCH_MAX * sizeof(BatchEntry);
-constexpr size_t kRecOff = kOutOff + DPOW_BATCH_MAX * sizeof(unsigned long long);
-constexpr size_t kHostBytes = kRecOff + 64;
+constexpr size_t kBatchMapOff = kEngineImageBytes;  // h_mem, behind the upload image
+constexpr size_t kBatchOutOff = kBatchMapOff + DPOW_BATCH_MAX * sizeof(BatchEntry);
+constexpr size_t kBatchRecOff = kBatchOutOff + DPOW_BATCH_MAX * sizeof(unsigned long long);
+constexpr size_t kBatchHostBytes = kBatchRecOff + 64;
 
 int batch_state(BatchState **state, hipStream_t stream) {
     if (*state) return 0;
     BatchState *s = new (std::nothrow) BatchState();
     if (!s) return set_error(DPOW_ENOMEM, "dpow_search_batch: out of memory");
-    hipError_t e;
-    if ((e = hipMalloc(&s->d_mem, kDevBytes)) != hipSuccess ||
-        (e = hipHostMalloc(&s->h_mem, kHostBytes, hipHostMallocCoherent | hipHostMallocMapped)) != hipSuccess ||
-        (e = hipHostGetDevicePointer(reinterpret_cast<void **>(&s->d_h_mem), s->h_mem, 0)) != hipSuccess ||
-        (e = hipMemsetAsync(s->d_mem + kCtlOff, 0, 64, stream)) != hipSuccess ||
-        (e = hipStreamSynchronize(stream)) != hipSuccess || (e = batch_prepare()) != hipSuccess) {
-        batch_free(s);
-        return hip_fail(e, "dpow_search_batch: allocation");
-    }
-    memset(s->h_mem, 0, kHostBytes);
-    *state = s;
-    return 0;
+    const int rc = engine_alloc(s->buf, kEngineDevBytes, kBatchHostBytes, stream, batch_prepare,
+                                "dpow_search_batch: allocation");
+    if (rc < 0) delete s;
+    else *state = s;
+    return rc;
 }
 
 }  // namespace
 
-// Wait for the completion record of launch `seq`: spin at first (a small round's record is a
-// few microseconds away), then sleep between polls; the stream is queried now and then so a
-// failed launch ends the wait with an error.
-int batch_wait_record(const BatchRecord *rec, uint32_t seq, hipStream_t stream, const char *idle_msg) {
-    const int64_t t0 = now_ns();
-    for (uint64_t it = 1;; ++it) {
-        if (__atomic_load_n(&rec->seq, __ATOMIC_ACQUIRE) == seq) return 0;
-        const bool spinning = now_ns() - t0 < 200000;
-        if (spinning ? (it % 4096 == 0) : (it % 16 == 0)) {
-            const int alive = stream_liveness(stream, &rec->seq, seq, idle_msg);
-            if (alive != 0) return alive < 0 ? alive : 0;
-        }
-        if (spinning) {
-            __builtin_ia32_pause();
-        } else {
-            const struct timespec ts = {0, 5000};
-            nanosleep(&ts, nullptr);
-        }
-    }
-}
-
-int batch_check_task(const dpow_batch_task &t, const char *who) {
-    const std::string w(who);
-    if (t.nonce_len && !t.nonce) return set_error(DPOW_EINVAL, w + ": nonce is NULL");
-    if (t.nonce_len > DPOW_MAX_NONCE) return set_error(DPOW_EINVAL, w + ": nonce longer than DPOW_MAX_NONCE");
-    if (t.worker_byte > 255u) return set_error(DPOW_EINVAL, w + ": worker_byte > 255");
-    if (t.k_begin > t.k_end) return set_error(DPOW_EINVAL, w + ": k_begin > k_end");
-    if (t.k_end > DPOW_K_LIMIT) return set_error(DPOW_ERANGE, w + ": k_end beyond DPOW_K_LIMIT");
-    return 0;
-}
-
 void batch_free(BatchState *s) {
     if (!s) return;
-    if (s->d_mem) (void)hipFree(s->d_mem);
-    if (s->h_mem) (void)hipHostFree(s->h_mem);
+    engine_free(s->buf);
     delete s;
 }
 
@@ -186,11 +124,8 @@ int batch_run(BatchState **state, hipStream_t stream, const volatile uint32_t *c
         for (size_t i = 0; i < n; ++i) {
             tasks[i].status = status[i];
             tasks[i].secret_len = 0;
-            if (status[i] != DPOW_FOUND) continue;
-            size_t len = 0;
-            dpow_secret_from_index(hit[i], tasks[i].secret, &len);
-            tasks[i].secret_len = (uint32_t)len;
-            tasks[i].best_global_idx = hit[i];
+            if (status[i] == DPOW_FOUND)
+                engine_write_hit(hit[i], tasks[i].secret, tasks[i].secret_len, tasks[i].best_global_idx);
         }
         if (stats) *stats = st;
     };
@@ -200,12 +135,12 @@ int batch_run(BatchState **state, hipStream_t stream, const volatile uint32_t *c
     }
     int rc = batch_state(state, stream);
     if (rc < 0) return rc;
-    BatchState *s = *state;
+    EngineBuffers &s = (*state)->buf;
+    const EngineSections at{n * sizeof(BatchTask), kBatchOutOff, kBatchRecOff};
 
-    // The upload image [BatchTask x n][best x n] and the live list.  A task with an empty
-    // window, or whose window starts at or above its bound, is exhausted without a launch.
-    BatchTask *img_tasks = reinterpret_cast<BatchTask *>(s->h_mem);
-    unsigned long long *img_best = reinterpret_cast<unsigned long long *>(s->h_mem + n * sizeof(BatchTask));
+    // The upload image [BatchTask x n][best x n] and the live list.
+    BatchTask *img_tasks = reinterpret_cast<BatchTask *>(s.h_mem);
+    unsigned long long *img_best = reinterpret_cast<unsigned long long *>(s.h_mem + at.best);
     std::vector<Live> live;
     live.reserve(n);
     for (size_t i = 0; i < n; ++i) {
@@ -213,71 +148,52 @@ int batch_run(BatchState **state, hipStream_t stream, const volatile uint32_t *c
         batch_fill_task(img_tasks[i], t.nonce, t.nonce_len, t.ntz, t.worker_byte, t.worker_bits);
         img_best[i] = t.best_global_idx;
         const uint32_t rbits = img_tasks[i].rbits;
-        if (t.k_begin >= t.k_end || (t.k_begin << 8) >= t.best_global_idx) {
+        if (window_needs_no_launch(t.k_begin, t.k_end, t.best_global_idx)) {
             status[i] = DPOW_EXHAUSTED;
             continue;
         }
-        live.push_back(Live{(uint32_t)i, t.k_begin << rbits, t.k_end << rbits});
+        live.push_back(Live{(uint32_t)i, t.k_begin << rbits, t.k_end << rbits, rbits, img_tasks[i].base_tb});
     }
     if (!live.empty()) {
         const hipError_t e =
-            batch_upload(reinterpret_cast<uint32_t *>(s->d_mem), reinterpret_cast<const uint32_t *>(s->d_h_mem),
+            batch_upload(reinterpret_cast<uint32_t *>(s.d_mem), reinterpret_cast<const uint32_t *>(s.d_h_mem),
                          (uint32_t)(n * (sizeof(BatchTask) + sizeof(unsigned long long)) / 4), stream);
         if (e != hipSuccess) return hip_fail(e, "dpow_search_batch: upload");
     }
-    BatchEntry *const h_map = reinterpret_cast<BatchEntry *>(s->h_mem + kMapOff);
-    const unsigned long long *const h_out = reinterpret_cast<const unsigned long long *>(s->h_mem + kOutOff);
-    const BatchRecord *const h_rec = reinterpret_cast<const BatchRecord *>(s->h_mem + kRecOff);
+    BatchEntry *const h_map = reinterpret_cast<BatchEntry *>(s.h_mem + kBatchMapOff);
+    const unsigned long long *const h_out = reinterpret_cast<const unsigned long long *>(s.h_mem + kBatchOutOff);
+    const BatchEntry *const d_map = reinterpret_cast<const BatchEntry *>(s.d_h_mem + kBatchMapOff);
+    const auto issue = [&](const BatchLaunch &L) {
+        const hipError_t e = batch_launch(reinterpret_cast<const BatchTask *>(s.d_mem), d_map, L, stream);
+        return e == hipSuccess ? 0 : hip_fail(e, "dpow_search_batch: launch");
+    };
     std::vector<BatchEntry> entries;
     std::vector<Live> next;
     for (uint32_t round = 0; !live.empty(); ++round) {
         if (__atomic_load_n(cancel, __ATOMIC_ACQUIRE) != 0u) break;  // the live tasks stay DPOW_CANCELLED
         const BatchRound r = plan_round(round, live, entries);
         memcpy(h_map, entries.data(), entries.size() * sizeof(BatchEntry));
-        BatchLaunch L{};
-        L.best = reinterpret_cast<unsigned long long *>(s->d_mem + n * sizeof(BatchTask));
-        L.out_best = reinterpret_cast<unsigned long long *>(s->d_h_mem + kOutOff);
-        L.rec = reinterpret_cast<BatchRecord *>(s->d_h_mem + kRecOff);
-        L.done = reinterpret_cast<uint32_t *>(s->d_mem + kCtlOff);
-        L.t0 = reinterpret_cast<unsigned long long *>(s->d_mem + kCtlOff + 8);
-        L.n_live = (uint32_t)live.size();
-        L.group = r.group;
-        L.n_blocks = r.rows * L.n_live;
-        if (++s->seq == 0u) s->seq = 1u;
-        L.seq = s->seq;
-        const hipError_t e = batch_launch(reinterpret_cast<const BatchTask *>(s->d_mem),
-                                          reinterpret_cast<const BatchEntry *>(s->d_h_mem + kMapOff), L, stream);
-        if (e != hipSuccess) return hip_fail(e, "dpow_search_batch: launch");
-        if ((rc = batch_wait_record(h_rec, L.seq, stream,
-                                    "dpow_search_batch: stream idle without the launch's completion record")) < 0)
-            return rc;
-        st.launches++;
-        st.rounds++;
-        if (h_rec->t_start != 0ull && h_rec->t_end >= h_rec->t_start)
-            st.kernel_ms += (double)(h_rec->t_end - h_rec->t_start) * kRealtimeNs * 1e-6;
+        const uint32_t n_live = (uint32_t)live.size();
+        rc = engine_launch(s, at, n_live, r.group, r.rows * n_live, stream,
+                           "dpow_search_batch: stream idle without the launch's completion record", st, issue);
+        if (rc < 0) return rc;
         next.clear();
         for (size_t j = 0; j < live.size(); ++j) {
             const Live &l = live[j];
             const dpow_batch_task &t = tasks[l.task];
             st.candidates += entries[j].i_end - entries[j].i_begin;
             const uint64_t b = h_out[j];
-            if (b < t.best_global_idx) {  // below the bound: a hit, re-verified on the host
-                uint8_t sec[DPOW_MAX_SECRET];
-                size_t len = 0;
-                dpow_secret_from_index(b, sec, &len);
-                if (!dpow_verify(t.nonce, t.nonce_len, sec, len, t.ntz))
+            switch (engine_settle(t.nonce, t.nonce_len, t.ntz, l.rbits, l.base_tb, t.best_global_idx, entries[j].i_end,
+                                  l.i_end, b)) {
+                case Settled::kVerifyFailed:
                     return set_error(DPOW_EVERIFY, "dpow_search_batch: kernel hit failed host MD5 verification");
-                status[l.task] = DPOW_FOUND;
-                hit[l.task] = b;
-                continue;
+                case Settled::kFound:
+                    status[l.task] = DPOW_FOUND;
+                    hit[l.task] = b;
+                    break;
+                case Settled::kExhausted: status[l.task] = DPOW_EXHAUSTED; break;
+                case Settled::kLive: next.push_back(Live{l.task, entries[j].i_end, l.i_end, l.rbits, l.base_tb}); break;
             }
-            const uint64_t cur = entries[j].i_end;
-            const BatchTask &bt = img_tasks[l.task];
-            if (cur >= l.i_end || global_of_local(cur, bt.rbits, bt.base_tb) >= t.best_global_idx) {
-                status[l.task] = DPOW_EXHAUSTED;
-                continue;
-            }
-            next.push_back(Live{l.task, cur, l.i_end});
         }
         live.swap(next);
     }

@@ -1,4 +1,5 @@
-// batch.h -- host side of the batched search (batch.cpp), as dpow_api.cpp sees it.
+// batch.h -- host side of the batched search (batch.cpp), as dpow_api.cpp sees it, and the round
+// schedule that the task queue's planner (queue.h) is built from.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -17,6 +18,11 @@ constexpr uint64_t kBatchMinSlice = 256;      // one workgroup step
 constexpr uint32_t kBatchBlocks = 4096;       // workgroups a launch aims for (16 per CU)
 constexpr uint32_t kBatchMinGroup = 256, kBatchMaxGroup = 16384;  // local indices per workgroup
 
+// What a batch hashes in all in round `step`; the task queue's budget of a task of that age.
+uint64_t batch_budget(uint32_t step);
+// Local indices per workgroup of a launch whose slices, as planned, sum to `total`.
+uint32_t batch_group(uint64_t total);
+
 struct BatchRound {
     uint64_t slice;  // local indices per live task
     uint32_t group;  // local indices per workgroup
@@ -27,17 +33,6 @@ BatchRound batch_round(uint32_t round, size_t n_live, uint64_t max_left);
 
 uint64_t pow2_floor(uint64_t x);  // 0 for 0
 uint64_t pow2_ceil(uint64_t x);
-
-// What the task queue (queue.cpp) shares with the batch's host loop: a task's table row, the
-// argument errors of one task (`who`: the entry point named in the message), and the wait for a
-// launch's completion record (the stream-liveness check included; `idle_msg`: the error text when
-// the stream went idle without the record).
-struct BatchTask;
-struct BatchRecord;
-void batch_fill_task(BatchTask &t, const uint8_t *nonce, size_t nonce_len, uint32_t ntz, uint32_t worker_byte,
-                     uint32_t worker_bits);
-int batch_check_task(const dpow_batch_task &t, const char *who);
-int batch_wait_record(const BatchRecord *rec, uint32_t seq, hipStream_t stream, const char *idle_msg);
 
 // Device and pinned buffers of a context's batches: allocated on its first batch, freed with it.
 struct BatchState;

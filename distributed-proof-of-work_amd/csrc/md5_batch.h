@@ -1,6 +1,7 @@
 // md5_batch.h -- the batched search (dpow_search_batch): definitions shared by the generic
-// gfx950 kernel (md5_batch.hip) and its host loop and planner (batch.cpp), and by the task queue
-// that launches the same kernel code one descriptor per workgroup (queue.cpp).
+// gfx950 kernel (md5_batch.hip), its host loop and planner (batch.cpp), the task queue that launches
+// the same kernel code one descriptor per workgroup (queue.cpp) and the launch engine under both
+// (batch_engine.h).
 //
 // One kernel hashes B independent tasks over one grid.  Unlike the specialised kernels of
 // md5_search_kernel.h, whose message layout (NBLK, W0, SH) is a template parameter, a batch mixes

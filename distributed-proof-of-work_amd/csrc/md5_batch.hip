@@ -17,7 +17,8 @@
 //
 // No wave waits for another wave or for the host: the grid is bounded, a workgroup's work is
 // fixed at its start, and the only cross-workgroup state is the retirement count whose last
-// increment copies the live tasks' best values and the completion record to pinned memory.
+// increment copies the live tasks' best values and the completion record to pinned memory
+// (retire_workgroup, the one tail of both entry points).
 #include <hip/hip_runtime.h>
 
 #include "md5_batch.h"
@@ -82,26 +83,20 @@ struct BatchGroup {
     }
 };
 
-__global__ void __launch_bounds__(kBlockThreads)
-    batch_kernel(const BatchTask *__restrict__ tasks, const BatchEntry *__restrict__ map, const BatchLaunch L) {
-    __shared__ uint32_t s_last;
+// The launch's start tick, from its first workgroup.
+__device__ __forceinline__ void launch_start_tick(const BatchLaunch &L) {
     if (blockIdx.x == 0 && threadIdx.x == 0)
         __hip_atomic_store(L.t0, __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const uint32_t row = blockIdx.x / L.n_live;
-    const uint32_t j = blockIdx.x - row * L.n_live;
-    const BatchEntry *const e = map + j;
-    uint64_t lo, hi;
-    if (batch_block_range(e->i_begin, e->i_end, row, L.group, lo, hi)) {
-        const uint32_t ti = e->task;
-        const BatchGroup g{tasks + ti, L.best + ti, lo, hi};
-        batch_with_w0(__builtin_amdgcn_readfirstlane(g.t->p >> 2), g);
-    }
-    // Retirement, counted per workgroup.  Each wave's atomicMin has been performed already (the
-    // hit path consumes the returning atomic's result), the barrier covers the four waves, so the
-    // count comes after every hit of the workgroup.  (An agent-scope release fence here instead
-    // cost every wave an L2 write-back: ~0.2 ms per launch of 4096 small workgroups.)  The
-    // workgroup whose count completes the launch copies the live tasks' best values out and
-    // writes the completion record, from one wave.
+}
+
+// Retirement, counted per workgroup.  Each wave's atomicMin has been performed already (the
+// hit path consumes the returning atomic's result), the barrier covers the four waves, so the
+// count comes after every hit of the workgroup.  (An agent-scope release fence here instead
+// cost every wave an L2 write-back: ~0.2 ms per launch of 4096 small workgroups.)  The
+// workgroup whose count completes the launch copies the live tasks' best values out --
+// out_best[q] = best of table slot slot_of(q) -- and writes the completion record, from one wave.
+template <typename SlotOf>
+__device__ __forceinline__ void retire_workgroup(const BatchLaunch &L, uint32_t &s_last, SlotOf slot_of) {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -112,7 +107,7 @@ __global__ void __launch_bounds__(kBlockThreads)
     if (s_last != 0u && threadIdx.x < 64u) {
         for (uint32_t q = threadIdx.x; q < L.n_live; q += 64u) {
             const unsigned long long b =
-                __hip_atomic_load(L.best + map[q].task, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_load(L.best + slot_of(q), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(L.out_best + q, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");  // the wave's stores before its lane 0's record
@@ -125,6 +120,22 @@ __global__ void __launch_bounds__(kBlockThreads)
             __hip_atomic_store(&L.rec->seq, L.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }
+}
+
+__global__ void __launch_bounds__(kBlockThreads)
+    batch_kernel(const BatchTask *__restrict__ tasks, const BatchEntry *__restrict__ map, const BatchLaunch L) {
+    __shared__ uint32_t s_last;
+    launch_start_tick(L);
+    const uint32_t row = blockIdx.x / L.n_live;
+    const uint32_t j = blockIdx.x - row * L.n_live;
+    const BatchEntry *const e = map + j;
+    uint64_t lo, hi;
+    if (batch_block_range(e->i_begin, e->i_end, row, L.group, lo, hi)) {
+        const uint32_t ti = e->task;
+        const BatchGroup g{tasks + ti, L.best + ti, lo, hi};
+        batch_with_w0(__builtin_amdgcn_readfirstlane(g.t->p >> 2), g);
+    }
+    retire_workgroup(L, s_last, [map](uint32_t q) { return map[q].task; });
 }
 
 // The upload image, pinned host memory to device memory (batch_upload).
@@ -145,8 +156,7 @@ __global__ void __launch_bounds__(kBlockThreads)
     queue_kernel(const BatchTask *__restrict__ tasks, const BatchEntry *__restrict__ blocks,
                  const uint32_t *__restrict__ out_slots, const BatchLaunch L) {
     __shared__ uint32_t s_last;
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        __hip_atomic_store(L.t0, __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    launch_start_tick(L);
     const BatchEntry *const e = blocks + blockIdx.x;
     const uint64_t lo = e->i_begin, hi = e->i_end;
     if (lo < hi) {
@@ -154,30 +164,7 @@ __global__ void __launch_bounds__(kBlockThreads)
         const BatchGroup g{tasks + ti, L.best + ti, lo, hi};
         batch_with_w0(__builtin_amdgcn_readfirstlane(g.t->p >> 2), g);
     }
-    // (see batch_kernel: every hit's atomicMin has returned, the barrier covers the four waves)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const uint32_t prev = __hip_atomic_fetch_add(L.done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_last = prev + 1u == L.n_blocks ? 1u : 0u;
-    }
-    __syncthreads();
-    if (s_last != 0u && threadIdx.x < 64u) {
-        for (uint32_t q = threadIdx.x; q < L.n_live; q += 64u) {
-            const unsigned long long b =
-                __hip_atomic_load(L.best + out_slots[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(L.out_best + q, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");  // the wave's stores before its lane 0's record
-        if (threadIdx.x == 0) {
-            __hip_atomic_store(L.done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const unsigned long long t_start = __hip_atomic_load(L.t0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(&L.rec->t_start, t_start, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __hip_atomic_store(&L.rec->t_end, __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_SYSTEM);
-            __hip_atomic_store(&L.rec->seq, L.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-    }
+    retire_workgroup(L, s_last, [out_slots](uint32_t q) { return out_slots[q]; });
 }
 
 // The rows of the task table that changed since the queue's last launch (newly filled slots), from

@@ -8,9 +8,11 @@
 // up with a kernel on the queue's stream, so a reused slot is rewritten in stream order), plan,
 // launch, wait for the completion record, read the live slots' best values, verify every hit with
 // the host MD5, decide, and age the survivors.  One launch is in flight; every launch is bounded.
+// The buffers, the launch up to its record and a task's fate after it are the launch engine's
+// (batch_engine.h), shared with dpow_search_batch.
 //
 // Planner (queue_plan, a pure host function; DESIGN.md "Task queue").  A task of age a (launches
-// it took part in) has the budget b = min(kBatchFirst * 4^a, kBatchCap) of a batch's round a.  A
+// it took part in) has the budget b = batch_budget(a) of a batch's round a.  A
 // launch hashes Bd = min(max b, kQueueSpread * min b): a launch that holds a fresh task stays
 // short.  Task i's ceiling is max(pow2_floor(min(b_i, Bd) / n_live), kBatchMinSlice), its share
 // of a batch of this size at its own age within this launch's budget; every task but those of
@@ -40,15 +42,12 @@
 
 #include "../../include/dpow.h"
 #include "../../include/dpow_worker.h"
+#include "batch_engine.h"
 #include "ctx.h"
 #include "md5_batch.h"
 #include "plan.h"
 
 namespace dpow {
-
-uint64_t queue_task_budget(uint32_t age) {
-    return std::min(kBatchFirst << (2 * std::min<uint32_t>(age, 8u)), kBatchCap);
-}
 
 void queue_plan(const uint64_t *left, const uint32_t *age, size_t n, QueuePlan &plan, uint64_t spread) {
     plan.slice.assign(n, 0);
@@ -60,7 +59,7 @@ void queue_plan(const uint64_t *left, const uint32_t *age, size_t n, QueuePlan &
     uint64_t min_b = ~0ull, max_b = 0, max_left = 0;
     uint32_t max_age = 0;
     for (size_t i = 0; i < n; ++i) {
-        const uint64_t b = queue_task_budget(age[i]);
+        const uint64_t b = batch_budget(age[i]);
         min_b = std::min(min_b, b);
         max_b = std::max(max_b, b);
         max_age = std::max(max_age, age[i]);
@@ -69,7 +68,7 @@ void queue_plan(const uint64_t *left, const uint32_t *age, size_t n, QueuePlan &
     const uint64_t budget = std::min(max_b, spread * min_b);
     const uint64_t longest = pow2_ceil(max_left);  // no blocks past the longest range left (batch_round)
     auto ceiling = [&](uint32_t a) {
-        return std::max(pow2_floor(std::min(queue_task_budget(a), budget) / (uint64_t)n), kBatchMinSlice);
+        return std::max(pow2_floor(std::min(batch_budget(a), budget) / (uint64_t)n), kBatchMinSlice);
     };
     // `total` sums the slices as planned, before a task's own end cuts its slice short: what
     // batch_round takes for the group.
@@ -92,8 +91,7 @@ void queue_plan(const uint64_t *left, const uint32_t *age, size_t n, QueuePlan &
         plan.slice[i] = std::min(share, left[i]);
         total += share;
     }
-    const uint64_t group = std::min<uint64_t>(std::max<uint64_t>(pow2_floor(total / kBatchBlocks), kBatchMinGroup),
-                                              kBatchMaxGroup);
+    const uint64_t group = batch_group(total);
     plan.budget = budget;
     plan.group = (uint32_t)group;
     // Blocks by ordinal, then by task: every task's early indices are dispatched first.  `active`
@@ -132,17 +130,20 @@ struct QTask {
     bool decided = false;  // its result exists (its slot is freed once no launch can write it)
 };
 
-constexpr size_t kRowsOff = 0;  // pinned: the rows of newly filled slots
-constexpr size_t kBlocksOff = kRowsOff + DPOW_BATCH_MAX * sizeof(QueueRow);
-constexpr size_t kSlotsOff = kBlocksOff + (size_t)kQueueMaxBlocks * sizeof(BatchEntry);
-constexpr size_t kOutOff = kSlotsOff + DPOW_BATCH_MAX * sizeof(uint32_t);
-constexpr size_t kRecOff = kOutOff + DPOW_BATCH_MAX * sizeof(unsigned long long);
-constexpr size_t kHostBytes = kRecOff + 64;
-constexpr size_t kBestOff = DPOW_BATCH_MAX * sizeof(BatchTask);  // device: the table, the best words, control
-constexpr size_t kCtlOff = kBestOff + DPOW_BATCH_MAX * sizeof(unsigned long long);  // done (u32) +0, t0 (u64) +8
-constexpr size_t kDevBlocksOff = kCtlOff + 64;  // the descriptor table of a launch of kQueueCopyBlocks or more
-constexpr size_t kDevBytes = kDevBlocksOff + (size_t)kQueueMaxBlocks * sizeof(BatchEntry);
-static_assert(kBlocksOff % 32 == 0 && kOutOff % 8 == 0 && kRecOff % 8 == 0, "aligned sections");
+// The queue's buffers (dpow_queue::buf).  Pinned: the rows of newly filled slots, a launch's
+// descriptors, its live-slot list, out_best, the record.  Device: the task table, the best words and
+// the control words (batch_engine.h), then the descriptor table of a launch of kQueueCopyBlocks or more.
+constexpr size_t kQueueRowsOff = 0;
+constexpr size_t kQueueBlocksOff = kQueueRowsOff + DPOW_BATCH_MAX * sizeof(QueueRow);
+constexpr size_t kQueueSlotsOff = kQueueBlocksOff + (size_t)kQueueMaxBlocks * sizeof(BatchEntry);
+constexpr size_t kQueueOutOff = kQueueSlotsOff + DPOW_BATCH_MAX * sizeof(uint32_t);
+constexpr size_t kQueueRecOff = kQueueOutOff + DPOW_BATCH_MAX * sizeof(unsigned long long);
+constexpr size_t kQueueHostBytes = kQueueRecOff + 64;
+constexpr size_t kQueueBestOff = DPOW_BATCH_MAX * sizeof(BatchTask);
+constexpr size_t kQueueDevBlocksOff = kEngineDevBytes;
+constexpr size_t kQueueDevBytes = kQueueDevBlocksOff + (size_t)kQueueMaxBlocks * sizeof(BatchEntry);
+static_assert(kQueueBlocksOff % 32 == 0 && kQueueOutOff % 8 == 0 && kQueueRecOff % 8 == 0, "aligned sections");
+constexpr EngineSections kQueueAt{kQueueBestOff, kQueueOutOff, kQueueRecOff};
 
 const char *const kIdleMsg = "dpow_queue: stream idle without the launch's completion record";
 
@@ -155,9 +156,7 @@ using namespace dpow;
 struct dpow_queue {
     int device = 0;
     dpow_ctx *ctx = nullptr;  // private: its stream carries the queue's launches
-    char *d_mem = nullptr;
-    char *h_mem = nullptr;    // pinned, mapped
-    char *d_h_mem = nullptr;  // its device alias
+    EngineBuffers buf;        // seq and the device side: the pump's alone
 
     std::mutex mu;
     std::condition_variable pump_cv;  // arrivals, close
@@ -173,7 +172,6 @@ struct dpow_queue {
     std::string fail_msg;
     bool closing = false;
     uint64_t next_ticket = 1;
-    uint32_t seq = 0;
     uint64_t spread = kQueueSpread;  // DPOW_DIAG_QUEUE_SPREAD at open: the A/B behind the constant (tools/queue_rate.py)
     dpow_batch_stats stats{};
     std::thread pump;
@@ -186,12 +184,7 @@ struct dpow_queue {
         r.user = t.user;
         r.status = status;
         r.global_idx = DPOW_NO_HIT;
-        if (status == DPOW_FOUND) {
-            size_t len = 0;
-            dpow_secret_from_index(hit, r.secret, &len);
-            r.secret_len = (uint32_t)len;
-            r.global_idx = hit;
-        }
+        if (status == DPOW_FOUND) engine_write_hit(hit, r.secret, r.secret_len, r.global_idx);
         r.launches = t.age;
         r.queued_ms = (double)(now_ns() - t.t_submit) * 1e-6;
         t.decided = true;
@@ -222,11 +215,29 @@ struct dpow_queue {
             fail(DPOW_EHIP, "dpow_queue: hipSetDevice failed in the pump thread");
             return;
         }
-        QueueRow *const h_rows = reinterpret_cast<QueueRow *>(h_mem + kRowsOff);
-        BatchEntry *const h_blocks = reinterpret_cast<BatchEntry *>(h_mem + kBlocksOff);
-        uint32_t *const h_slots = reinterpret_cast<uint32_t *>(h_mem + kSlotsOff);
-        const unsigned long long *const h_out = reinterpret_cast<const unsigned long long *>(h_mem + kOutOff);
-        const BatchRecord *const h_rec = reinterpret_cast<const BatchRecord *>(h_mem + kRecOff);
+        QueueRow *const h_rows = reinterpret_cast<QueueRow *>(buf.h_mem + kQueueRowsOff);
+        BatchEntry *const h_blocks = reinterpret_cast<BatchEntry *>(buf.h_mem + kQueueBlocksOff);
+        uint32_t *const h_slots = reinterpret_cast<uint32_t *>(buf.h_mem + kQueueSlotsOff);
+        const unsigned long long *const h_out = reinterpret_cast<const unsigned long long *>(buf.h_mem + kQueueOutOff);
+        BatchTask *const d_tasks = reinterpret_cast<BatchTask *>(buf.d_mem);
+        uint32_t *const d_blocks = reinterpret_cast<uint32_t *>(buf.d_mem + kQueueDevBlocksOff);
+        const uint32_t *const p_blocks = reinterpret_cast<const uint32_t *>(buf.d_h_mem + kQueueBlocksOff);  // pinned
+        uint32_t n_rows = 0;
+        // The rows of new slots, then the launch.  A short descriptor table is read where it is, in
+        // pinned memory, one scalar load per workgroup; a long one is first copied to device memory
+        // by the upload kernel (queue.h kQueueCopyBlocks).
+        const auto issue = [&](const BatchLaunch &L) {
+            hipError_t e = queue_upload(d_tasks, L.best, reinterpret_cast<const QueueRow *>(buf.d_h_mem + kQueueRowsOff),
+                                        n_rows, ctx->stream);
+            const bool copy = L.n_blocks >= kQueueCopyBlocks;
+            if (e == hipSuccess && copy)
+                e = batch_upload(d_blocks, p_blocks, L.n_blocks * (uint32_t)(sizeof(BatchEntry) / 4), ctx->stream);
+            if (e == hipSuccess)
+                e = queue_launch(d_tasks, reinterpret_cast<const BatchEntry *>(copy ? d_blocks : p_blocks),
+                                 reinterpret_cast<const uint32_t *>(buf.d_h_mem + kQueueSlotsOff), L, ctx->stream);
+            return e == hipSuccess ? 0 : hip_fail(e, "dpow_queue: launch");
+        };
+        dpow_batch_stats run{};  // launches, rounds and kernel time, counted with the mutex dropped
         std::vector<std::shared_ptr<QTask>> in_launch;
         std::vector<uint64_t> left;
         std::vector<uint32_t> age;
@@ -243,7 +254,7 @@ struct dpow_queue {
                 }
             }
             live_slots.resize(keep);
-            uint32_t n_rows = 0;
+            n_rows = 0;
             while (!arrivals.empty() && !free_slots.empty()) {
                 std::shared_ptr<QTask> t = arrivals.front();
                 arrivals.pop_front();
@@ -287,64 +298,33 @@ struct dpow_queue {
                 e.task = live_slots[pb.task];
                 e.pad_[0] = e.pad_[1] = e.pad_[2] = 0;
             }
-            BatchLaunch L{};
-            L.best = reinterpret_cast<unsigned long long *>(d_mem + kBestOff);
-            L.out_best = reinterpret_cast<unsigned long long *>(d_h_mem + kOutOff);
-            L.rec = reinterpret_cast<BatchRecord *>(d_h_mem + kRecOff);
-            L.done = reinterpret_cast<uint32_t *>(d_mem + kCtlOff);
-            L.t0 = reinterpret_cast<unsigned long long *>(d_mem + kCtlOff + 8);
-            L.n_live = (uint32_t)n;
-            L.group = plan.group;
-            L.n_blocks = (uint32_t)plan.blocks.size();
-            if (++seq == 0u) seq = 1u;
-            L.seq = seq;
-            g.unlock();
-            int rc = 0;
-            hipError_t e = queue_upload(reinterpret_cast<BatchTask *>(d_mem), L.best,
-                                        reinterpret_cast<const QueueRow *>(d_h_mem + kRowsOff), n_rows, ctx->stream);
-            // A short table is read where it is, in pinned memory, one scalar load per workgroup; a
-            // long one is first copied to device memory by the upload kernel (queue.h kQueueCopyBlocks).
-            const BatchEntry *d_blocks = reinterpret_cast<const BatchEntry *>(d_h_mem + kBlocksOff);
-            if (e == hipSuccess && L.n_blocks >= kQueueCopyBlocks) {
-                e = batch_upload(reinterpret_cast<uint32_t *>(d_mem + kDevBlocksOff),
-                                 reinterpret_cast<const uint32_t *>(d_h_mem + kBlocksOff),
-                                 L.n_blocks * (uint32_t)(sizeof(BatchEntry) / 4), ctx->stream);
-                d_blocks = reinterpret_cast<const BatchEntry *>(d_mem + kDevBlocksOff);
-            }
-            if (e == hipSuccess)
-                e = queue_launch(reinterpret_cast<const BatchTask *>(d_mem), d_blocks,
-                                 reinterpret_cast<const uint32_t *>(d_h_mem + kSlotsOff), L, ctx->stream);
-            if (e != hipSuccess) rc = hip_fail(e, "dpow_queue: launch");
-            else rc = batch_wait_record(h_rec, L.seq, ctx->stream, kIdleMsg);
+            g.unlock();  // round the upload, the launch and the wait
+            const int rc = engine_launch(buf, kQueueAt, (uint32_t)n, plan.group, (uint32_t)plan.blocks.size(), ctx->stream,
+                                         kIdleMsg, run, issue);
             g.lock();
             if (rc < 0) {
                 fail(rc, dpow_last_error());
                 return;
             }
-            stats.launches++;
-            stats.rounds++;
-            if (h_rec->t_start != 0ull && h_rec->t_end >= h_rec->t_start)
-                stats.kernel_ms += (double)(h_rec->t_end - h_rec->t_start) * kRealtimeNs * 1e-6;
+            stats.launches = run.launches;
+            stats.rounds = run.rounds;
+            stats.kernel_ms = run.kernel_ms;
             for (size_t j = 0; j < n; ++j) {
                 QTask &t = *in_launch[j];
                 stats.candidates += plan.slice[j];
                 t.age++;
                 if (t.decided) continue;  // cancelled while the launch ran: the kill wins over its hit
                 const uint64_t b = h_out[j];
-                if (b < t.bound) {  // below the bound: a hit, re-verified on the host
-                    uint8_t sec[DPOW_MAX_SECRET];
-                    size_t len = 0;
-                    dpow_secret_from_index(b, sec, &len);
-                    if (!dpow_verify(t.nonce.data(), t.nonce.size(), sec, len, t.ntz)) {
+                t.i_cur += plan.slice[j];
+                switch (engine_settle(t.nonce.data(), t.nonce.size(), t.ntz, t.rbits, t.base_tb, t.bound, t.i_cur,
+                                      t.i_end, b)) {
+                    case Settled::kVerifyFailed:
                         fail(DPOW_EVERIFY, "dpow_queue: kernel hit failed host MD5 verification");
                         return;
-                    }
-                    decide(t, DPOW_FOUND, b);
-                    continue;
+                    case Settled::kFound: decide(t, DPOW_FOUND, b); break;
+                    case Settled::kExhausted: decide(t, DPOW_EXHAUSTED, DPOW_NO_HIT); break;
+                    case Settled::kLive: break;
                 }
-                t.i_cur += plan.slice[j];
-                if (t.i_cur >= t.i_end || global_of_local(t.i_cur, t.rbits, t.base_tb) >= t.bound)
-                    decide(t, DPOW_EXHAUSTED, DPOW_NO_HIT);
             }
             for (auto &t : in_launch) t.reset();
         }
@@ -392,19 +372,15 @@ int dpow_queue_open(int device, dpow_queue **out) {
         if (v >= 1 && v <= 256) q->spread = (uint64_t)v;  // Bd stays within kBatchCap: the block table holds any launch
     }
     const DeviceScope on_device(device);
-    hipError_t e = on_device.e;
-    if (e != hipSuccess || (e = hipMalloc(&q->d_mem, kDevBytes)) != hipSuccess ||
-        (e = hipHostMalloc(&q->h_mem, kHostBytes, hipHostMallocCoherent | hipHostMallocMapped)) != hipSuccess ||
-        (e = hipHostGetDevicePointer(reinterpret_cast<void **>(&q->d_h_mem), q->h_mem, 0)) != hipSuccess ||
-        (e = hipMemsetAsync(q->d_mem + kCtlOff, 0, 64, ctx->stream)) != hipSuccess ||
-        (e = hipStreamSynchronize(ctx->stream)) != hipSuccess || (e = queue_prepare()) != hipSuccess) {
-        if (q->d_mem) (void)hipFree(q->d_mem);
-        if (q->h_mem) (void)hipHostFree(q->h_mem);
-        dpow_close(ctx);
+    const char *const who = "dpow_queue_open: allocation";
+    const int arc = on_device.e != hipSuccess
+                        ? hip_fail(on_device.e, who)
+                        : engine_alloc(q->buf, kQueueDevBytes, kQueueHostBytes, ctx->stream, queue_prepare, who);
+    if (arc < 0) {
+        dpow_close(ctx);  // (leaves the thread's error as it is)
         delete q;
-        return hip_fail(e, "dpow_queue_open: allocation");
+        return arc;
     }
-    memset(q->h_mem, 0, kHostBytes);
     q->slot_task.resize(DPOW_BATCH_MAX);
     q->free_slots.reserve(DPOW_BATCH_MAX);
     for (uint32_t s = DPOW_BATCH_MAX; s-- > 0;) q->free_slots.push_back(s);  // slot 0 first
@@ -429,8 +405,7 @@ void dpow_queue_close(dpow_queue *q) {
     {
         const DeviceScope on_device(q->device);
         (void)hipStreamSynchronize(q->ctx->stream);
-        if (q->d_mem) (void)hipFree(q->d_mem);
-        if (q->h_mem) (void)hipHostFree(q->h_mem);
+        engine_free(q->buf);
     }
     dpow_close(q->ctx);
     delete q;
@@ -472,7 +447,7 @@ int dpow_queue_submit(dpow_queue *q, const uint8_t *nonce, size_t nonce_len, uin
         return set_error(DPOW_EAGAIN, "dpow_queue_submit: DPOW_BATCH_MAX tasks are undecided or not yet collected");
     t->ticket = q->next_ticket++;
     *ticket = t->ticket;
-    if (k_begin >= k_end || (k_begin << 8) >= bound) {  // as dpow_search_batch: exhausted without a launch
+    if (window_needs_no_launch(k_begin, k_end, bound)) {  // as dpow_search_batch
         q->decide(*t, DPOW_EXHAUSTED, DPOW_NO_HIT);
         return 0;
     }

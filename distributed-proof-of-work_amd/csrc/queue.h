@@ -27,9 +27,6 @@ constexpr uint32_t kQueueMaxBlocks = 32768;
 // from a few hundred descriptors on.
 constexpr uint32_t kQueueCopyBlocks = 256;
 
-// What a batch hashes in all in the round a task of this age would be in (batch_round's target).
-uint64_t queue_task_budget(uint32_t age);
-
 struct QueueBlock {
     uint32_t task;     // index into the planner's inputs
     uint32_t ordinal;  // of the block within its task's slice
@@ -44,7 +41,8 @@ struct QueuePlan {
     std::vector<QueueBlock> blocks;   // descriptor order: by ordinal, then by task
 };
 
-// One launch for n live tasks: left[i] > 0 local indices to go, age[i] launches taken part in.
+// One launch for n live tasks: left[i] > 0 local indices to go, age[i] launches taken part in (its
+// budget is batch_budget(age[i]), the launch's group batch_group of the slices as planned).
 // `spread` is kQueueSpread but for the A/B override of dpow_queue_open (DPOW_DIAG_QUEUE_SPREAD).
 void queue_plan(const uint64_t *left, const uint32_t *age, size_t n, QueuePlan &plan, uint64_t spread = kQueueSpread);
 
