@@ -61,6 +61,14 @@ constexpr uint32_t kBop3I = 0x39;  // I = y ^ (x | ~z)
 constexpr int kNC = DPOW_NC;
 constexpr int kWaveBlock = 64 * kNC;  // local indices per wave-block
 constexpr int kBlockThreads = 256;    // 4 waves per workgroup
+// Wave-blocks per poll group of a long search: a wave polls Ctrl::best / Ctrl::stop once per
+// group of Launch::poll_wb wave-blocks of a chunk (the host's choice: plan.h launch_poll_wb; the
+// kernels whose KernelTune::kPoll is false compile this value in).  profiles/r01_ab_poll.log:
+// once per chunk / 12 / 16 / 32 wave-blocks -> 216.3 / 217.8 / 218.3 / 218.6 GH/s,
+// time-to-secret N=7 1.57 / 1.47 / 1.49 / 1.56 ms.
+#ifndef DPOW_POLL_WB
+#define DPOW_POLL_WB 16
+#endif
 // Claim counters per launch: one per XCD (workgroup b runs on XCD b % 8), each
 // on its own 128-byte line.  Counter x hands out chunks x, x + 8, x + 16, ...
 // in increasing order, so the early exit stays exact per counter, and eight
@@ -132,7 +140,7 @@ struct Launch {
     uint64_t n_static;     // claims [0, n_static) are handed out by wave index, not by a counter: worker
                            //  wave w's first claim is w (the "_ls" kernels only; 0 for every other launch)
     uint32_t poll_wb;      // wave-blocks per group: a wave reads Ctrl::best / Ctrl::stop once per group
-    uint32_t n_seg;        // segment-inner launches (md5_search_kernel.h search_body_si): the 2^24-k segments
+    uint32_t n_seg;        // segment-inner launches (md5_search_si.h search_body_si): the 2^24-k segments
                            //  the window lies in; wb_begin / n_wblocks / the claims then describe ONE
                            //  segment's index range.  0: every other launch (index order)
     unsigned long long *claim;  // this launch's kClaimCounters counters (zero at launch start;
@@ -211,7 +219,7 @@ DPOW_HD uint32_t tail_prefilter_le(uint32_t n) {
     return e == 0 ? 0xFFFFFFFFu : e >= 8 ? 0u : (0xFFFFFFFFu >> (4 * e));
 }
 
-// Layouts with a segment-inner kernel (md5_search_kernel.h search_body_si; md5_variant.hip's "_si"
+// Layouts with a segment-inner kernel (md5_search_si.h search_body_si; md5_variant.hip's "_si"
 // unit): one final block, SH = 0, W0 <= 3 (nonces of 0, 4, 8 and 12 bytes).
 DPOW_HD bool seg_inner_layout(uint32_t nblk, uint32_t w0, uint32_t sh) { return nblk == 1 && sh == 0 && w0 <= 3; }
 

@@ -21,23 +21,24 @@ using namespace DPOW_KNS;
 using KernelFn = void (*)(Launch);
 // EQ kernels (the D-equality test, use_d_equality) exist for one final block only.
 // The kernel of a layout: the long-SGPR-budget template for long nonces and two
-// final blocks (md5_search_kernel.h kLongSgpr), a slightly larger budget for the two-block
-// W0 = 15 layouts and a few more (kW15Sgpr); only the chosen one is instantiated.
+// final blocks, a slightly larger budget for the two-block W0 = 15 layouts and a few more
+// (md5_kernel_tune.h KernelTune::kSgpr); only the chosen one is instantiated.
 template <int NBLK, int W0, int SH, bool EQ, bool KSPAN>
 constexpr KernelFn kernel_of() {
-    if constexpr (kSgprOf<NBLK, W0, SH, KSPAN> == 2) return md5_search_kernel_w15sgpr<NBLK, W0, SH, EQ, KSPAN>;
-    else if constexpr (kSgprOf<NBLK, W0, SH, KSPAN> == 1) return md5_search_kernel_lsgpr<NBLK, W0, SH, EQ, KSPAN>;
+    constexpr int kSgpr = KernelTune<NBLK, W0, SH, KSPAN>::kSgpr;
+    if constexpr (kSgpr == 2) return md5_search_kernel_w15sgpr<NBLK, W0, SH, EQ, KSPAN>;
+    else if constexpr (kSgpr == 1) return md5_search_kernel_lsgpr<NBLK, W0, SH, EQ, KSPAN>;
     else return md5_search_kernel<NBLK, W0, SH, EQ, KSPAN>;
 }
 // [EQ][narrow][w0 - kW0Lo]: narrow = the SH = 3 kernel without the lanes' k offset
 // (md5_search_kernel.h hash_wave_block KSPAN), for launches with R >= 64, where narrow_knobs
-// has one; other layouts have one kernel for both.
+// (md5_kernel_tune.h) has one; other layouts have one kernel for both.
 #define DPOW_K(w, e, nar) \
     kernel_of<DPOW_VNBLK, w, DPOW_VSH, e, !(DPOW_VSH == 3 && nar && narrow_knobs(DPOW_VNBLK, w).on)>()
 #if DPOW_VSI
 // The segment-inner unit: one final block, SH = 0, the D-equality test, W0 <= 3 (nonces of 0, 4,
 // 8 and 12 bytes): the invariants cost ~10 VGPRs more per W0 of compiler-scheduled lead-in, and
-// from W0 = 4 on the kernels pass the 72-VGPR cap of VgprK (73-78).
+// from W0 = 4 on the kernels pass the 72-VGPR cap of KernelTune::kCap (73-78).
 #if DPOW_VNBLK != 1 || DPOW_VSH != 0
 #error "the segment-inner unit is built for NBLK = 1, SH = 0"
 #endif

@@ -35,7 +35,7 @@ inline bool variant_exists(int nblk, int w0, int sh) {
 // Launches whose template is chunk length 0's (L.seg0 == kLsegBase: SH = 0 below k = 2^24)
 // run the "_ls" kernels.  (No timing events: the kernel stamps its start and end into its
 // completion record.)
-// True when a segment-inner kernel exists for the layout (md5_search_kernel.h search_body_si).
+// True when a segment-inner kernel exists for the layout (md5_search_si.h search_body_si).
 inline bool seg_inner_exists(int nblk, int w0, int sh) {
     return w0 >= 0 && seg_inner_layout((uint32_t)nblk, (uint32_t)w0, (uint32_t)sh);
 }

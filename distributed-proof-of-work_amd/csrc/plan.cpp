@@ -211,7 +211,7 @@ void candidate_words(const PlannedLaunch &pl, uint64_t local_idx, uint32_t words
     const uint32_t lane = (uint32_t)(local_idx & 63u);
     uint32_t seg_of_idx = (uint32_t)((local_idx >> Lh.rbits) >> 24);
     if (Lh.n_seg != 0u) {
-        // segment-inner (md5_search_kernel.h search_body_si): V from the wave-block's offset in
+        // segment-inner (md5_search_si.h search_body_si): V from the wave-block's offset in
         // the first segment's range, the segment word from the segment's number in the launch
         const uint32_t segbits = 24u + Lh.rbits;
         const uint64_t rel = i0 - Lh.wb_begin;
@@ -222,7 +222,7 @@ void candidate_words(const PlannedLaunch &pl, uint64_t local_idx, uint32_t words
     const uint32_t sh = pl.info.sh, w0 = pl.info.w0;
     words[w0] += V << (8 * sh);
     if (sh) words[w0 + 1] += V >> (32 - 8 * sh);
-    if (Lh.seg0 == kLsegBase && !pl.k0) {  // SH = 0 below 2^24: md5_search_kernel.h seg_all_deltas
+    if (Lh.seg0 == kLsegBase && !pl.k0) {  // SH = 0 below 2^24: md5_hash.h seg_all_deltas
         uint32_t d0, d1, dlen;
         // (the kernel takes a group's chunk length from its first index at or above i_begin)
         lseg_deltas(chunk_len_of(local_idx >> Lh.rbits), d0, d1, dlen);
@@ -235,7 +235,7 @@ void candidate_words(const PlannedLaunch &pl, uint64_t local_idx, uint32_t words
         words[w0 + 1] += d1;
         words[lenw] += dlen;
     }
-    {  // the segment words, as the kernel re-derives them (md5_search_kernel.h seg_word)
+    {  // the segment words, as the kernel re-derives them (md5_hash.h seg_word)
         uint32_t d1, d2;
         const uint32_t seg = seg_of_idx;
         seg_word_deltas(Lh.T[w0 + 1], Lh.T[w0 + 2], seg, Lh.seg_first, sh, d1, d2);
@@ -308,7 +308,7 @@ int size_launch(PlannedLaunch &pl, uint64_t max_blocks, uint64_t expect, uint64_
     L.n_big = n_big;
     L.n_chunks = n_chunks;
     L.n_head = 2 * worker_blocks * wpb;
-    // Static first claims (md5_search_kernel.h kStaticFirst): the "_ls" kernels (the
+    // Static first claims (md5_kernel_tune.h kStaticFirst): the "_ls" kernels (the
     // chunk-length-0 template, L.seg0 == kLsegBase) hand claim w to worker wave w.  Every
     // counter that holds a claim beyond them still has a workgroup (checked above on
     // n_chunks, which bounds the counters' share too).

@@ -100,12 +100,9 @@ uint64_t expected_first_hit(uint32_t ntz, uint32_t rbits);
 // Wave-blocks per poll group (Launch::poll_wb).  A wave reads Ctrl::best / Ctrl::stop
 // once per group, issued before the group and consumed after it, so a hit elsewhere,
 // an injected bound (the node board) or a cancel reaches it within two groups.  Long
-// groups cost less issue (DPOW_POLL_WB = 16 for searches expected to run for more than
-// kFastPollCands candidates -- the sweep, N >= 9), short ones (kFastPollWb) shorten the
+// groups cost less issue (dpow_common.h DPOW_POLL_WB = 16 for searches expected to run for more
+// than kFastPollCands candidates -- the sweep, N >= 9), short ones (kFastPollWb) shorten the
 // drain after a hit when the whole search is expected to be short.
-#ifndef DPOW_POLL_WB
-#define DPOW_POLL_WB 16  // (also md5_search_kernel.h)
-#endif
 // Round 4 (the early Found fan-out, the claim-ahead in a chunk's last group): searches
 // expected beyond kMidExpect poll every 8 wave-blocks (round 3: 4), those up to it every 4.
 // An 8-GPU node, emulated (tools/node_probe.py, profiles/r04_node_ab.log r04ab6): [2,2,2,2]/8
@@ -260,7 +257,7 @@ constexpr int64_t kShareLaunchNs = (int64_t)DPOW_SHARE_LAUNCH_US * 1000;
 constexpr double kEstRate = 2.3e11;  // candidates/s of one device (bench: 217-218 on the one-block layouts)
 uint64_t grid_share(uint64_t active, const LaunchKnobs &knobs);
 
-// Segment-inner launches (md5_search_kernel.h search_body_si): a wave keeps its wave-block and
+// Segment-inner launches (md5_search_si.h search_body_si): a wave keeps its wave-block and
 // walks the launch's 2^24-k segments, so the work that depends on word W0 alone is done once
 // per wave-block instead of once per candidate (about 2 % fewer VALU instructions).  The price:
 // a hit is found out of index order, so the launch drains whole -- at most one launch of extra

@@ -8,7 +8,7 @@
 // plan.cpp).  (Round 3 start: this kernel also reset the control block and
 // claim counters, in front of the first md5 launch on the same stream -- 15 us on every
 // search's time-to-secret path; the launches now reset the next search's control block
-// themselves, md5_search_kernel.h publish().)
+// themselves, md5_launch_ctl.h publish().)
 #include <hip/hip_runtime.h>
 
 #include "dpow_common.h"

@@ -83,7 +83,7 @@ int dpow_diag_launch_geometry(const uint8_t *nonce, size_t nonce_len, uint32_t n
 
 /* The same for segment-inner launches, as their kernel gets them: wb_begin is the first
  * segment's first index, n_wblocks one segment's wave-blocks, the claims cover those, and a
- * wave hashes each wave-block in every one of the n_seg segments (md5_search_kernel.h
+ * wave hashes each wave-block in every one of the n_seg segments (md5_search_si.h
  * search_body_si).  mode: -1 the search's policy, 0 never, 1 wherever the shape permits
  * (the DPOW_DIAG_SEG_INNER environment knob of dpow_open).  The device is not shared. */
 int dpow_diag_seg_inner_geometry(const uint8_t *nonce, size_t nonce_len, uint32_t ntz, uint32_t worker_byte,

@@ -26,7 +26,7 @@ Every case is also checked against SURVEY.md Appendix A where the survey lists i
     section 8(d) item 5), the config-1/2/5 nonces at N = 9, and [1,2,3,4] at N = 10.
 
   * --seg-inner: tests/golden/seg_inner_hits.json, all-hits lists for the
-    segment-inner kernels (md5_search_kernel.h search_body_si).  Each case is
+    segment-inner kernels (md5_search_si.h search_body_si).  Each case is
     {name, nonce, k_begin, k_end, hits: [[g, tz], ...]}: every candidate
     g = k * 256 + threadByte of the workerBits = 0 window [k_begin, k_end) whose
     hex digest ends in >= 8 '0' characters, with its actual trailing-'0' count,

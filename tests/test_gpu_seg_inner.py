@@ -1,4 +1,4 @@
-"""GPU: the segment-inner kernels (md5_search_kernel.h search_body_si) find exactly what the
+"""GPU: the segment-inner kernels (md5_search_si.h search_body_si) find exactly what the
 index-ordered kernels find.
 
 The path is forced with DPOW_DIAG_SEG_INNER=1 (read at dpow_open), so N = 8 searches -- ~1 hit

@@ -1,4 +1,4 @@
-"""GPU: every segment-inner kernel (md5_search_kernel.h search_body_si) against hit lists that do
+"""GPU: every segment-inner kernel (md5_search_si.h search_body_si) against hit lists that do
 not come from this library.
 
 tests/golden/seg_inner_hits.json lists every N >= 8 hit of nine workerBits = 0 windows with its

@@ -1,6 +1,6 @@
 """Static checks of the segment-inner sweep kernel's gfx950 code (no GPU needed).
 
-The segment-inner kernel (md5_search_kernel.h search_body_si, the "_si" unit) hashes a
+The segment-inner kernel (md5_search_si.h search_body_si, the "_si" unit) hashes a
 wave-block once per 2^24-k segment from lane invariants computed once per wave-block: step
 W0 whole, step W0 + 1's bitop3 and the three later K + M[W0] adds leave the per-candidate
 work.  Its hash block -- one segment's hash of a wave-block, <1,1,0> with the D-equality
@@ -54,7 +54,7 @@ def test_pipeline_order_and_padding(kernel_si):
     _, lines = kernel_si
     m = {"v_bitop3_b32": "F", "v_add_u32_e32": "F", "v_add3_u32": "H", "v_alignbit_b32": "H", "s_nop": "n"}
     seq = "".join(m.get(l.split()[0], ".") for l in lines if re.search(r"//\s*[0-9A-F]{6,}:", l)).replace(".", "")
-    group = "FHnHnFHnFFHn"  # md5_search_kernel.h DPOW_PIPE_BODY
+    group = "FHnHnFHnFFHn"  # md5_hash.h DPOW_PIPE_BODY
     assert seq.count(group) >= 50, seq[:400]
     body = seq[seq.find(group):seq.rfind(group) + len(group)]
     assert "HF" not in body and "HH" not in body

@@ -48,7 +48,7 @@ def si_geometry(nonce, ntz, wb, wbits, k0, k1, mode=-1, cus=256):
 
 
 def check_si(d):
-    """The claim geometry of a segment-inner launch (md5_search_kernel.h search_body_si)."""
+    """The claim geometry of a segment-inner launch (md5_search_si.h search_body_si)."""
     W = d.wave_block
     segbits = 24 + d.rbits
     assert d.k_begin >= SEG and d.k_end - d.k_begin >= 2 * SEG

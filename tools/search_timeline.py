@@ -29,7 +29,7 @@ import distpow  # noqa: E402
 from distpow._lib import LaunchTime  # noqa: E402
 from distpow.node import NodeBoard, node_mine, owner_rank  # noqa: E402
 
-W, F = 8192, 8  # the diag build's per-wave trace (md5_search_kernel.h DPOW_WAVE_TRACE)
+W, F = 8192, 8  # the diag build's per-wave trace (md5_launch_ctl.h WaveTrace)
 CASES = [([1, 2, 3, 4], 3), ([5, 6, 7, 8], 5), ([2, 2, 2, 2], 5), ([1, 2, 3, 4], 6)]
 RUNS = 5
 

@@ -9,7 +9,7 @@ import distpow
 from distpow import _lib
 
 W = 6144
-F = 8  # words per wave (md5_search_kernel.h kTraceFields)
+F = 8  # words per wave (md5_launch_ctl.h kTraceFields)
 lib = ctypes.CDLL(_lib.LIB_PATH)
 m = distpow.Miner(0)
 m.search([1, 2, 3, 4], 32, 0, 0, 1 << 24, (1 << 24) + (1 << 24))  # warm the clock
