@@ -133,6 +133,7 @@ struct LaunchSlot {
 };
 
 struct BatchState;  // batch.h
+struct ScanState;   // scan.h
 
 // The body of dpow_search (arguments checked): search.cpp.
 int search_window(dpow_ctx *c, const uint8_t *nonce, size_t nonce_len, uint32_t ntz, uint32_t worker_byte,
@@ -197,6 +198,7 @@ struct __attribute__((visibility("default"))) dpow_ctx {
     // the young-search rule (plan.h kYoungNs) does not share the device with the idle ranks.
     bool solo = false;
     dpow::BatchState *batch = nullptr;  // buffers of dpow_search_batch: allocated by the first batch (batch.cpp)
+    dpow::ScanState *scan = nullptr;    // buffers of dpow_scan: allocated by the first scan (scan.cpp)
 };
 
 namespace dpow {

@@ -1,7 +1,7 @@
 // dpow_api.cpp -- the C ABI (include/dpow.h) over the gfx950 search kernels: the context's
 // lifecycle (dpow_open, dpow_close), its accessors and stats, the argument-checking entry points
-// of the searches (dpow_search: search.cpp; dpow_search_batch: batch.cpp; dpow_search_bound) and
-// the pure host helpers.  The node layer is node.cpp, the dpow_diag_* entry points diag.cpp.
+// of the searches (dpow_search: search.cpp; dpow_search_batch: batch.cpp; dpow_scan: scan.cpp;
+// dpow_search_bound) and the pure host helpers.  The node layer is node.cpp, the dpow_diag_* entry points diag.cpp.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -10,9 +10,11 @@
 #include <algorithm>
 
 #include "batch.h"
+#include "batch_engine.h"
 #include "ctx.h"
 #include "md5_host.h"
 #include "md5_variants.h"
+#include "scan.h"
 
 using namespace dpow;
 
@@ -176,6 +178,7 @@ void dpow_close(dpow_ctx *c) {
     c->node = c->d_node = nullptr;
     pages_release_ctx(c);
     batch_free(c->batch);
+    scan_free(c->scan);
     if (c->d_ctrl_alloc) (void)hipFree(c->d_ctrl_alloc);
     if (c->d_claims) (void)hipFree(c->d_claims);
     if (c->h_snap) (void)hipHostFree(c->h_snap);
@@ -276,6 +279,33 @@ int dpow_search_batch(dpow_ctx *c, dpow_batch_task *tasks, size_t n_tasks, dpow_
     if (on_device.e != hipSuccess) return hip_fail(on_device.e, "hipSetDevice");
     c->last_use.store(now_ns(), std::memory_order_relaxed);
     return batch_run(&c->batch, c->stream, c->h_cancel, tasks, n_tasks, stats);
+}
+
+int dpow_scan(dpow_ctx *c, const uint8_t *nonce, size_t nonce_len, uint32_t ntz, uint32_t worker_byte,
+              uint32_t worker_bits, uint64_t k_begin, uint64_t k_end, dpow_scan_hit *out, size_t max_hits,
+              size_t *n_hits, uint64_t *k_done, dpow_batch_stats *stats) {
+    if (!out || !n_hits || !k_done) return set_error(DPOW_EINVAL, "dpow_scan: NULL argument");
+    if (max_hits < 256) return set_error(DPOW_EINVAL, "dpow_scan: max_hits below 256 (one k's candidates)");
+    dpow_batch_task t{};  // the window's own errors first: they need no context
+    t.nonce = nonce;
+    t.nonce_len = nonce_len;
+    t.worker_byte = worker_byte;
+    t.k_begin = k_begin;
+    t.k_end = k_end;
+    const int rc = batch_check_task(t, "dpow_scan");
+    if (rc < 0) return rc;
+    if (!c) return set_error(DPOW_EINVAL, "dpow_scan: ctx is NULL");
+    if (c->node) return set_error(DPOW_EINVAL, "dpow_scan: a node slot is attached to the context");
+    *n_hits = 0;
+    *k_done = k_begin;
+    if (stats) *stats = dpow_batch_stats{};
+    if (k_begin == k_end) return DPOW_EXHAUSTED;  // (*k_done = k_end)
+    if (__atomic_load_n(c->h_cancel, __ATOMIC_ACQUIRE) != 0u) return DPOW_CANCELLED;  // raised on entry: no launch
+    const DeviceScope on_device(c->device);
+    if (on_device.e != hipSuccess) return hip_fail(on_device.e, "hipSetDevice");
+    c->last_use.store(now_ns(), std::memory_order_relaxed);
+    return scan_run(&c->scan, c->stream, c->h_cancel, nonce, nonce_len, ntz, worker_byte, worker_bits, k_begin, k_end,
+                    out, max_hits, n_hits, k_done, stats);
 }
 
 int dpow_search(dpow_ctx *c, const uint8_t *nonce, size_t nonce_len, uint32_t ntz, uint32_t worker_byte,

@@ -12,6 +12,9 @@
 //   dpow_cli batch <ntz> <nonce-hex> [<nonce-hex> ...] [--device N]
 //       mine every nonce from k = 0 in one batched search (dpow_search_batch), window by window;
 //       one line per task: its global index and its secret in hex
+//   dpow_cli scan <nonce-hex> <ntz> <k_begin> <k_end> [worker_byte worker_bits [device]]
+//       every hit of the window (dpow_scan), one line per hit: its global index, its depth and its
+//       secret in hex
 // Each other command prints one JSON line.
 #include <stdio.h>
 #include <stdlib.h>
@@ -237,7 +240,35 @@ static int cmd_batch(int argc, char **argv) {
     return 0;
 }
 
+static int cmd_scan(int argc, char **argv) {
+    if (argc < 6) return 2;
+    std::vector<uint8_t> nonce = from_hex(argv[2]);
+    const uint32_t ntz = (uint32_t)atoi(argv[3]);
+    uint64_t k = strtoull(argv[4], nullptr, 0);
+    const uint64_t k_end = strtoull(argv[5], nullptr, 0);
+    const uint32_t wb = argc > 7 ? (uint32_t)atoi(argv[6]) : 0, wbits = argc > 7 ? (uint32_t)atoi(argv[7]) : 0;
+    const int dev = argc > 8 ? atoi(argv[8]) : 0;
+    dpow_ctx *ctx = nullptr;
+    int rc = dpow_open(dev, &ctx);
+    if (rc) return fail("dpow_open", rc);
+    std::vector<dpow_scan_hit> page(1u << 16);
+    do {
+        size_t n = 0;
+        rc = dpow_scan(ctx, nonce.data(), nonce.size(), ntz, wb, wbits, k, k_end, page.data(), page.size(), &n, &k,
+                       nullptr);
+        if (rc < 0) return fail("dpow_scan", rc);
+        for (size_t i = 0; i < n; ++i) {
+            printf("%llu %u ", (unsigned long long)page[i].global_idx, page[i].tz);
+            for (uint32_t b = 0; b < page[i].secret_len; ++b) printf("%02x", page[i].secret[b]);
+            printf("\n");
+        }
+    } while (rc == DPOW_MORE);
+    dpow_close(ctx);
+    return rc == DPOW_EXHAUSTED ? 0 : 1;
+}
+
 int main(int argc, char **argv) {
+    if (argc >= 2 && !strcmp(argv[1], "scan")) return cmd_scan(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "batch")) return cmd_batch(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "mine")) return cmd_mine(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "sweep")) return cmd_sweep(argc, argv);
@@ -248,6 +279,7 @@ int main(int argc, char **argv) {
             "       dpow_cli sweep <log2-candidates> [device]\n"
             "       dpow_cli worker <nonce-hex> <ntz> [device]\n"
             "       dpow_cli latency [reps [device]]\n"
-            "       dpow_cli batch <ntz> <nonce-hex> [<nonce-hex> ...] [--device N]\n");
+            "       dpow_cli batch <ntz> <nonce-hex> [<nonce-hex> ...] [--device N]\n"
+            "       dpow_cli scan <nonce-hex> <ntz> <k_begin> <k_end> [worker_byte worker_bits [device]]\n");
     return 2;
 }

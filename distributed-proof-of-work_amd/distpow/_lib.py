@@ -93,6 +93,16 @@ class BatchRange(ctypes.Structure):
                 ("i_end", ctypes.c_uint64), ("group", ctypes.c_uint32), ("rows", ctypes.c_uint32)]
 
 
+MORE = 3  # dpow_scan: the hit array is full; call again from k_done
+SCAN_CAP = 1 << 16  # entries of a scan launch's hit list (csrc/md5_scan.h kScanCap)
+
+
+class ScanHitC(ctypes.Structure):
+    """dpow_scan_hit (include/dpow.h)."""
+    _fields_ = [("global_idx", ctypes.c_uint64), ("tz", ctypes.c_uint32), ("secret_len", ctypes.c_uint32),
+                ("secret", ctypes.c_uint8 * DPOW_MAX_SECRET)]
+
+
 class QueueResultC(ctypes.Structure):
     """dpow_queue_result (include/dpow.h)."""
     _fields_ = [("ticket", ctypes.c_uint64), ("user", ctypes.c_uint64), ("status", ctypes.c_int32),
@@ -266,6 +276,10 @@ def lib():
                                            ctypes.c_size_t, u64p]),
         "dpow_batch_plan_block": (ctypes.c_int, [ctypes.POINTER(BatchRange), ctypes.c_uint32, ctypes.c_uint32,
                                                  u32p, u64p, u64p]),
+        "dpow_scan": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32,
+                                     ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ScanHitC),
+                                     ctypes.c_size_t, szp, u64p, ctypes.POINTER(BatchStats)]),
+        "dpow_scan_slice": (ctypes.c_uint64, [ctypes.c_uint32, ctypes.c_uint32]),
         "dpow_queue_open": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(vp)]),
         "dpow_queue_close": (None, [vp]),
         "dpow_queue_submit": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32,

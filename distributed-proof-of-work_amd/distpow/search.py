@@ -7,6 +7,7 @@ Names and argument meaning follow the reference: nonce, num_trailing_zeros
 (NumTrailingZeros), worker_byte (WorkerByte), worker_bits (WorkerBits).
 """
 import ctypes
+import struct
 from dataclasses import dataclass
 from typing import List, Optional, Sequence
 
@@ -15,7 +16,7 @@ from ._lib import (CANCELLED, DPOW_K_LIMIT, DPOW_MAX_SECRET, DPOW_NO_HIT, EXHAUS
                    PlanLaunch, Stats, check, lib)
 
 __all__ = ["Miner", "SearchResult", "BatchTask", "batch_candidate", "batch_plan", "batch_plan_block",
-           "TaskQueue", "QueueResult", "queue_plan",
+           "TaskQueue", "QueueResult", "queue_plan", "ScanHit", "scan_slice",
            "secret_from_index", "md5", "verify", "trailing_zero_nibbles",
            "thread_bytes", "remainder_bits", "global_index", "plan_window", "plan_candidate",
            "device_count", "DPOW_NO_HIT", "FOUND", "EXHAUSTED", "CANCELLED"]
@@ -158,6 +159,23 @@ def queue_plan(left: Sequence[int], age: Sequence[int]):
     arr = (_lib.BatchRange * max(cnt, 1))()
     check(lib().dpow_queue_plan(la, aa, n, arr, cnt, ctypes.byref(budget)), "dpow_queue_plan")
     return (_lib.BatchRange * cnt).from_buffer(arr), budget.value
+
+
+_SCAN_HIT = struct.Struct(f"<QII{DPOW_MAX_SECRET}s")  # dpow_scan_hit
+assert _SCAN_HIT.size == ctypes.sizeof(_lib.ScanHitC)
+
+
+@dataclass(frozen=True)
+class ScanHit:
+    """One hit of Miner.scan (dpow_scan_hit)."""
+    global_idx: int  # k * 256 + threadByte
+    tz: int          # trailing '0' characters of its digest, from the host MD5
+    secret: bytes    # threadByte || chunk_k
+
+
+def scan_slice(num_trailing_zeros: int, capacity: int = _lib.SCAN_CAP) -> int:
+    """Local indices per launch of a scan whose hit list holds `capacity` entries (dpow_scan_slice)."""
+    return lib().dpow_scan_slice(num_trailing_zeros, capacity)
 
 
 @dataclass
@@ -376,6 +394,37 @@ class Miner:
                 k[i] = t.k_end
             todo = [i for i in todo if out[i] is None]
         return out
+
+    # -- scan -------------------------------------------------------------------
+    def scan_page(self, nonce: Sequence[int], num_trailing_zeros: int, worker_byte: int = 0, worker_bits: int = 0,
+                  k_begin: int = 0, k_end: int = 1, max_hits: int = _lib.SCAN_CAP):
+        """One dpow_scan call: (status, hits, k_done).  EXHAUSTED: the window is done; MORE: `hits`
+        are all hits of [k_begin, k_done) and the caller continues from k_done; CANCELLED likewise.
+        The call's launch counts are kept in last_scan_stats."""
+        n = _b(nonce)
+        arr = (_lib.ScanHitC * max(max_hits, 1))()
+        cnt, k_done, st = ctypes.c_size_t(), ctypes.c_uint64(), _lib.BatchStats()
+        r = check(lib().dpow_scan(self._ctx, n, len(n), num_trailing_zeros, worker_byte, worker_bits, k_begin, k_end,
+                                  arr, max_hits, ctypes.byref(cnt), ctypes.byref(k_done), ctypes.byref(st)),
+                  "dpow_scan")
+        self.last_scan_stats = st
+        raw = ctypes.string_at(arr, cnt.value * _SCAN_HIT.size)
+        hits = [ScanHit(g, tz, sec[:slen]) for g, tz, slen, sec in _SCAN_HIT.iter_unpack(raw)]
+        return r, hits, k_done.value
+
+    def scan(self, nonce: Sequence[int], num_trailing_zeros: int, worker_byte: int = 0, worker_bits: int = 0,
+             k_begin: int = 0, k_end: int = 1, max_hits: int = _lib.SCAN_CAP) -> List[ScanHit]:
+        """Every candidate of the partition over k in [k_begin, k_end) whose digest ends in at least
+        num_trailing_zeros '0' characters, in increasing global index, each with its depth
+        (dpow_scan, paged over MORE; max_hits is the page size).  A raised cancel flag ends the scan
+        early with the hits found so far (see `cancelled`; scan_page tells how far it got)."""
+        out: List[ScanHit] = []
+        k = k_begin
+        while True:
+            r, hits, k = self.scan_page(nonce, num_trailing_zeros, worker_byte, worker_bits, k, k_end, max_hits)
+            out += hits
+            if r != _lib.MORE:
+                return out
 
     # -- measurement ------------------------------------------------------------
     def stats(self) -> Stats:

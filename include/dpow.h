@@ -34,7 +34,8 @@ extern "C" {
  * The batch entry points (dpow_search_batch, dpow_batch_candidate, dpow_batch_plan,
  * dpow_batch_plan_block) were added within ABI 5: nothing older changed, and the Python binding
  * refuses a library that lacks a prototype it lists, or one built from another tree.
- * The task queue (dpow_queue_*, DPOW_EAGAIN) and dpow_worker_set_queue were added the same way.
+ * The task queue (dpow_queue_*, DPOW_EAGAIN) and dpow_worker_set_queue were added the same way,
+ * and so was the scan (dpow_scan, dpow_scan_slice, DPOW_MORE).
  * A consumer built against another version must refuse the library before any
  * other call (distpow/_lib.py check_abi, tests/c/abi_harness.c). */
 #define DPOW_ABI_VERSION 5
@@ -159,6 +160,48 @@ typedef struct dpow_batch_stats {
     double kernel_ms;             /* sum of the launches' durations, as they stamp them */
 } dpow_batch_stats;
 int dpow_search_batch(dpow_ctx *ctx, dpow_batch_task *tasks, size_t n_tasks, dpow_batch_stats *stats);
+
+/* ---------------------------------------------------------------------------
+ * Scan (added within ABI 5): every hit of a window in one pass.
+ *
+ * Every search above answers "the first hit of a window".  dpow_scan reports every candidate
+ * of partition (worker_byte, worker_bits) over k in [k_begin, k_end) whose digest ends in at
+ * least ntz '0' characters, in increasing global index -- the reference's order, so dpow_search
+ * started at a hit's k returns that hit -- each with its depth.  It is what a cache that keeps a
+ * nonce's dominant secret (more zeros, else the greater bytes: worker.go's cache rule), a
+ * difficulty calibration or an audit asks.  Every entry is recomputed with the host MD5 before it
+ * is written (tz is the host's value; the device reports indices only); a device entry that fails
+ * verification is DPOW_EVERIFY.
+ *
+ * One generic kernel (csrc/md5_scan.hip) appends the hits of one bounded launch per slice of the
+ * window to a list.
+ *
+ * Returns DPOW_EXHAUSTED (0): the window is done, *k_done = k_end.  DPOW_MORE: `out` could not
+ * take the next k's hits; out[0..*n_hits) holds all hits of [k_begin, *k_done) and the caller
+ * continues with k_begin = *k_done.  A k's hits are never split over two calls, and max_hits
+ * < 256 is DPOW_EINVAL, so one k (at most 256 candidates) always fits and every call makes
+ * progress.  DPOW_CANCELLED: the context's cancel flag is raised (checked on entry, where it
+ * costs no launch, and between launches); the hits of [k_begin, *k_done) are complete.
+ * The argument errors are those of dpow_search_batch, returned before any GPU work: DPOW_EINVAL
+ * for a NULL pointer (stats may be NULL), worker_byte > 255, k_begin > k_end, a nonce longer than
+ * DPOW_MAX_NONCE or a context with a node slot attached; DPOW_ERANGE for k_end > DPOW_K_LIMIT.
+ * ntz = 0 is legal and makes every candidate a hit; ntz > 32 scans and finds nothing; an empty
+ * window is DPOW_EXHAUSTED without a launch.  One scan, search or batch is in flight per
+ * context.  dpow_search_bound has no effect on a scan, and a scan does not touch dpow_stats:
+ * its counts go to *stats.
+ * ------------------------------------------------------------------------- */
+#define DPOW_MORE 3            /* dpow_scan: `out` is full; call again from *k_done */
+typedef struct dpow_scan_hit {
+    uint64_t global_idx;       /* k * 256 + threadByte */
+    uint32_t tz;               /* trailing '0' characters of its digest (>= ntz), from the host MD5 */
+    uint32_t secret_len;
+    uint8_t secret[DPOW_MAX_SECRET];
+} dpow_scan_hit;
+int dpow_scan(dpow_ctx *ctx, const uint8_t *nonce, size_t nonce_len, uint32_t ntz,
+              uint32_t worker_byte, uint32_t worker_bits, uint64_t k_begin, uint64_t k_end,
+              dpow_scan_hit *out, size_t max_hits, size_t *n_hits, uint64_t *k_done,
+              dpow_batch_stats *stats /* may be NULL */);
+/* (dpow_scan_slice, the scan's slice rule, is with the host helpers below.) */
 
 /* ---------------------------------------------------------------------------
  * Task queue (added within ABI 5): the batched search as a service on one GPU.
@@ -446,6 +489,13 @@ int dpow_batch_plan_block(const dpow_batch_range *entries, uint32_t n_live, uint
  * DPOW_BATCH_MAX, a left[i] of 0); *budget_out = the launch's candidate budget. */
 int dpow_queue_plan(const uint64_t *left, const uint32_t *age, size_t n_tasks,
                     dpow_batch_range *out, size_t max_blocks, uint64_t *budget_out);
+
+/* The scan's slice rule (host logic of dpow_scan, exposed for testing):
+ * the local indices one launch of a scan for `ntz` covers when its hit list holds `capacity`
+ * entries (clamped to [256, 65536]; dpow_scan's own is 65536).  A multiple of 256 in
+ * [256, 2^28]; its expected hits, slice / 16^min(ntz, 32), are at most capacity / 4 wherever
+ * the slice is above 256. */
+uint64_t dpow_scan_slice(uint32_t ntz, uint32_t capacity);
 
 /* ---------------------------------------------------------------------------
  * Introspection / measurement.

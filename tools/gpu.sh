@@ -29,6 +29,8 @@
 #                    and the 8-thread paths (tools/batch_rate.py -> batch_rate.json)
 #   queue [reps]     the task queue's GPU tests, then its rate and latency tables (tools/queue_rate.py ->
 #                    queue_rate.json)
+#   scan [reps]      the scan's GPU tests, then its rate beside batch_kernel's, the walk against the scan
+#                    and the dense cost (tools/scan_rate.py -> scan_rate.json)
 set -o pipefail
 task=${1:?task}; tag=${2:?tag}; shift 2
 out=gpurun_out/$tag
@@ -114,6 +116,10 @@ queue)
         > $out/pytest_queue.txt 2>&1 &&
     timeout -k 10 400 python3 -u tools/queue_rate.py --reps "${1:-5}" --out $out/queue_rate.json \
         > $out/queue_rate.txt 2> $out/queue_rate.err ;;
+scan)
+    timeout -k 10 300 python3 -u -m pytest tests/test_gpu_scan.py -m gpu -x -v -s > $out/pytest_scan.txt 2>&1 &&
+    timeout -k 10 300 python3 -u tools/scan_rate.py --reps "${1:-5}" --out $out/scan_rate.json \
+        > $out/scan_rate.txt 2> $out/scan_rate.err ;;
 ab) timeout -k 10 800 python3 -u tools/ab_variants.py "$@" > $out/ab.log 2>&1 ;;
 node-ab)
     runs=$1; shift
