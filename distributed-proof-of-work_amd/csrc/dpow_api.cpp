@@ -1,7 +1,7 @@
 // dpow_api.cpp -- the C ABI (include/dpow.h) over the gfx950 search kernels: the context's
 // lifecycle (dpow_open, dpow_close), its accessors and stats, the argument-checking entry points
 // of the searches (dpow_search: search.cpp; dpow_search_batch: batch.cpp; dpow_scan: scan.cpp;
-// dpow_search_bound) and the pure host helpers.  The node layer is node.cpp, the dpow_diag_* entry points diag.cpp.
+// dpow_census_window: census.cpp; dpow_search_bound) and the pure host helpers.  The node layer is node.cpp, the dpow_diag_* entry points diag.cpp.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -11,6 +11,7 @@
 
 #include "batch.h"
 #include "batch_engine.h"
+#include "census.h"
 #include "ctx.h"
 #include "md5_host.h"
 #include "md5_variants.h"
@@ -179,6 +180,7 @@ void dpow_close(dpow_ctx *c) {
     pages_release_ctx(c);
     batch_free(c->batch);
     scan_free(c->scan);
+    census_free(c->census);
     if (c->d_ctrl_alloc) (void)hipFree(c->d_ctrl_alloc);
     if (c->d_claims) (void)hipFree(c->d_claims);
     if (c->h_snap) (void)hipHostFree(c->h_snap);
@@ -306,6 +308,32 @@ int dpow_scan(dpow_ctx *c, const uint8_t *nonce, size_t nonce_len, uint32_t ntz,
     c->last_use.store(now_ns(), std::memory_order_relaxed);
     return scan_run(&c->scan, c->stream, c->h_cancel, nonce, nonce_len, ntz, worker_byte, worker_bits, k_begin, k_end,
                     out, max_hits, n_hits, k_done, stats);
+}
+
+int dpow_census_window(dpow_ctx *c, const uint8_t *nonce, size_t nonce_len, uint32_t worker_byte,
+                       uint32_t worker_bits, uint64_t k_begin, uint64_t k_end, dpow_census *out, uint64_t *k_done,
+                       dpow_batch_stats *stats) {
+    if (!out || !k_done) return set_error(DPOW_EINVAL, "dpow_census_window: NULL argument");
+    dpow_batch_task t{};  // the window's own errors first: they need no context
+    t.nonce = nonce;
+    t.nonce_len = nonce_len;
+    t.worker_byte = worker_byte;
+    t.k_begin = k_begin;
+    t.k_end = k_end;
+    const int rc = batch_check_task(t, "dpow_census_window");
+    if (rc < 0) return rc;
+    if (!c) return set_error(DPOW_EINVAL, "dpow_census_window: ctx is NULL");
+    if (c->node) return set_error(DPOW_EINVAL, "dpow_census_window: a node slot is attached to the context");
+    census_clear(*out);
+    *k_done = k_begin;
+    if (stats) *stats = dpow_batch_stats{};
+    if (k_begin == k_end) return DPOW_EXHAUSTED;  // (*k_done = k_end)
+    if (__atomic_load_n(c->h_cancel, __ATOMIC_ACQUIRE) != 0u) return DPOW_CANCELLED;  // raised on entry: no launch
+    const DeviceScope on_device(c->device);
+    if (on_device.e != hipSuccess) return hip_fail(on_device.e, "hipSetDevice");
+    c->last_use.store(now_ns(), std::memory_order_relaxed);
+    return census_run(&c->census, c->stream, c->h_cancel, nonce, nonce_len, worker_byte, worker_bits, k_begin, k_end,
+                      out, k_done, stats);
 }
 
 int dpow_search(dpow_ctx *c, const uint8_t *nonce, size_t nonce_len, uint32_t ntz, uint32_t worker_byte,

@@ -15,6 +15,10 @@
 //   dpow_cli scan <nonce-hex> <ntz> <k_begin> <k_end> [worker_byte worker_bits [device]]
 //       every hit of the window (dpow_scan), one line per hit: its global index, its depth and its
 //       secret in hex
+//   dpow_cli census <nonce-hex> <k_begin> <k_end> [worker_byte worker_bits [device]]
+//       how deep the window goes (dpow_census_window), one line per depth up to the deepest: the
+//       depth, the number of candidates at least that deep, the first one's global index and its
+//       secret in hex
 // Each other command prints one JSON line.
 #include <stdio.h>
 #include <stdlib.h>
@@ -267,7 +271,33 @@ static int cmd_scan(int argc, char **argv) {
     return rc == DPOW_EXHAUSTED ? 0 : 1;
 }
 
+static int cmd_census(int argc, char **argv) {
+    if (argc < 5) return 2;
+    std::vector<uint8_t> nonce = from_hex(argv[2]);
+    const uint64_t k_begin = strtoull(argv[3], nullptr, 0), k_end = strtoull(argv[4], nullptr, 0);
+    const uint32_t wb = argc > 6 ? (uint32_t)atoi(argv[5]) : 0, wbits = argc > 6 ? (uint32_t)atoi(argv[6]) : 0;
+    const int dev = argc > 7 ? atoi(argv[7]) : 0;
+    dpow_ctx *ctx = nullptr;
+    int rc = dpow_open(dev, &ctx);
+    if (rc) return fail("dpow_open", rc);
+    dpow_census c;
+    uint64_t k_done = 0;
+    rc = dpow_census_window(ctx, nonce.data(), nonce.size(), wb, wbits, k_begin, k_end, &c, &k_done, nullptr);
+    if (rc < 0) return fail("dpow_census_window", rc);
+    for (uint32_t d = 0; d <= c.deepest && c.count_ge[d] > 0; ++d) {
+        uint8_t sec[DPOW_MAX_SECRET];
+        size_t len = 0;
+        dpow_secret_from_index(c.first_ge[d], sec, &len);
+        printf("%u %llu %llu ", d, (unsigned long long)c.count_ge[d], (unsigned long long)c.first_ge[d]);
+        for (size_t b = 0; b < len; ++b) printf("%02x", sec[b]);
+        printf("\n");
+    }
+    dpow_close(ctx);
+    return rc == DPOW_EXHAUSTED ? 0 : 1;
+}
+
 int main(int argc, char **argv) {
+    if (argc >= 2 && !strcmp(argv[1], "census")) return cmd_census(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "scan")) return cmd_scan(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "batch")) return cmd_batch(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "mine")) return cmd_mine(argc, argv);
@@ -280,6 +310,7 @@ int main(int argc, char **argv) {
             "       dpow_cli worker <nonce-hex> <ntz> [device]\n"
             "       dpow_cli latency [reps [device]]\n"
             "       dpow_cli batch <ntz> <nonce-hex> [<nonce-hex> ...] [--device N]\n"
-            "       dpow_cli scan <nonce-hex> <ntz> <k_begin> <k_end> [worker_byte worker_bits [device]]\n");
+            "       dpow_cli scan <nonce-hex> <ntz> <k_begin> <k_end> [worker_byte worker_bits [device]]\n"
+            "       dpow_cli census <nonce-hex> <k_begin> <k_end> [worker_byte worker_bits [device]]\n");
     return 2;
 }

@@ -103,6 +103,15 @@ class ScanHitC(ctypes.Structure):
                 ("secret", ctypes.c_uint8 * DPOW_MAX_SECRET)]
 
 
+CENSUS_DEPTHS = 33  # depths 0..32 (include/dpow.h DPOW_CENSUS_DEPTHS)
+
+
+class CensusC(ctypes.Structure):
+    """dpow_census (include/dpow.h)."""
+    _fields_ = [("count_ge", ctypes.c_uint64 * CENSUS_DEPTHS), ("first_ge", ctypes.c_uint64 * CENSUS_DEPTHS),
+                ("first_tz", ctypes.c_uint32 * CENSUS_DEPTHS), ("deepest", ctypes.c_uint32)]
+
+
 class QueueResultC(ctypes.Structure):
     """dpow_queue_result (include/dpow.h)."""
     _fields_ = [("ticket", ctypes.c_uint64), ("user", ctypes.c_uint64), ("status", ctypes.c_int32),
@@ -280,6 +289,10 @@ def lib():
                                      ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ScanHitC),
                                      ctypes.c_size_t, szp, u64p, ctypes.POINTER(BatchStats)]),
         "dpow_scan_slice": (ctypes.c_uint64, [ctypes.c_uint32, ctypes.c_uint32]),
+        "dpow_census_window": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32,
+                                              ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(CensusC), u64p,
+                                              ctypes.POINTER(BatchStats)]),
+        "dpow_census_merge": (ctypes.c_int, [ctypes.POINTER(CensusC), ctypes.POINTER(CensusC)]),
         "dpow_queue_open": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(vp)]),
         "dpow_queue_close": (None, [vp]),
         "dpow_queue_submit": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32,

@@ -16,7 +16,7 @@ from ._lib import (CANCELLED, DPOW_K_LIMIT, DPOW_MAX_SECRET, DPOW_NO_HIT, EXHAUS
                    PlanLaunch, Stats, check, lib)
 
 __all__ = ["Miner", "SearchResult", "BatchTask", "batch_candidate", "batch_plan", "batch_plan_block",
-           "TaskQueue", "QueueResult", "queue_plan", "ScanHit", "scan_slice",
+           "TaskQueue", "QueueResult", "queue_plan", "ScanHit", "scan_slice", "Census",
            "secret_from_index", "md5", "verify", "trailing_zero_nibbles",
            "thread_bytes", "remainder_bits", "global_index", "plan_window", "plan_candidate",
            "device_count", "DPOW_NO_HIT", "FOUND", "EXHAUSTED", "CANCELLED"]
@@ -176,6 +176,50 @@ class ScanHit:
 def scan_slice(num_trailing_zeros: int, capacity: int = _lib.SCAN_CAP) -> int:
     """Local indices per launch of a scan whose hit list holds `capacity` entries (dpow_scan_slice)."""
     return lib().dpow_scan_slice(num_trailing_zeros, capacity)
+
+
+@dataclass(frozen=True)
+class Census:
+    """Depth counts and per-depth first hits of a window (dpow_census, Miner.census).  A candidate's
+    depth is the number of trailing '0' characters of its digest; every tuple has 33 entries, d = 0..32."""
+    count_ge: tuple  # candidates with depth >= d (count_ge[0]: the window's size)
+    first_ge: tuple  # lowest global index with depth >= d (Miner.search's answer at d), None where absent
+    first_tz: tuple  # that candidate's depth, from the host MD5 (0 where absent)
+    deepest: int     # the largest d with count_ge[d] > 0 (0 of an empty window)
+
+    @classmethod
+    def empty(cls) -> "Census":
+        return cls((0,) * _lib.CENSUS_DEPTHS, (None,) * _lib.CENSUS_DEPTHS, (0,) * _lib.CENSUS_DEPTHS, 0)
+
+    @classmethod
+    def _from_c(cls, c) -> "Census":
+        return cls(tuple(c.count_ge), tuple(None if g == DPOW_NO_HIT else g for g in c.first_ge),
+                   tuple(c.first_tz), c.deepest)
+
+    def _to_c(self):
+        c = _lib.CensusC()
+        for d in range(_lib.CENSUS_DEPTHS):
+            c.count_ge[d] = self.count_ge[d]
+            c.first_ge[d] = DPOW_NO_HIT if self.first_ge[d] is None else self.first_ge[d]
+            c.first_tz[d] = self.first_tz[d]
+        c.deepest = self.deepest
+        return c
+
+    def exact(self, d: int) -> int:
+        """Candidates of depth exactly d."""
+        return self.count_ge[d] - (self.count_ge[d + 1] if d + 1 < _lib.CENSUS_DEPTHS else 0)
+
+    def secret(self, d: int) -> Optional[bytes]:
+        """The secret of first_ge[d] (threadByte || chunk_k), None where absent."""
+        return None if self.first_ge[d] is None else secret_from_index(self.first_ge[d])
+
+    def merged(self, other: "Census") -> "Census":
+        """This census followed by the census of a window that lies wholly above it
+        (dpow_census_merge); DpowError with code EINVAL when it does not, or either is not
+        self-consistent."""
+        into, nxt = self._to_c(), other._to_c()
+        check(lib().dpow_census_merge(ctypes.byref(into), ctypes.byref(nxt)), "dpow_census_merge")
+        return Census._from_c(into)
 
 
 @dataclass
@@ -425,6 +469,28 @@ class Miner:
             out += hits
             if r != _lib.MORE:
                 return out
+
+    # -- census -----------------------------------------------------------------
+    def census_page(self, nonce: Sequence[int], worker_byte: int = 0, worker_bits: int = 0, k_begin: int = 0,
+                    k_end: int = 1):
+        """One dpow_census_window call: (status, census, k_done).  EXHAUSTED: the window is done;
+        CANCELLED: `census` is the complete census of [k_begin, k_done) and the caller continues from
+        k_done and merges.  The call's launch counts are kept in last_census_stats."""
+        n = _b(nonce)
+        c, k_done, st = _lib.CensusC(), ctypes.c_uint64(), _lib.BatchStats()
+        r = check(lib().dpow_census_window(self._ctx, n, len(n), worker_byte, worker_bits, k_begin, k_end,
+                                           ctypes.byref(c), ctypes.byref(k_done), ctypes.byref(st)),
+                  "dpow_census_window")
+        self.last_census_stats = st
+        return r, Census._from_c(c), k_done.value
+
+    def census(self, nonce: Sequence[int], worker_byte: int = 0, worker_bits: int = 0, k_begin: int = 0,
+               k_end: int = 1) -> Census:
+        """How deep the partition's window k in [k_begin, k_end) goes: for every depth d the number of
+        candidates whose digest ends in at least d '0' characters and the first of them
+        (dpow_census_window).  A raised cancel flag ends it early with the census of the part done
+        (see `cancelled`; census_page tells how far it got)."""
+        return self.census_page(nonce, worker_byte, worker_bits, k_begin, k_end)[1]
 
     # -- measurement ------------------------------------------------------------
     def stats(self) -> Stats:

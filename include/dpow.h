@@ -35,7 +35,8 @@ extern "C" {
  * dpow_batch_plan_block) were added within ABI 5: nothing older changed, and the Python binding
  * refuses a library that lacks a prototype it lists, or one built from another tree.
  * The task queue (dpow_queue_*, DPOW_EAGAIN) and dpow_worker_set_queue were added the same way,
- * and so was the scan (dpow_scan, dpow_scan_slice, DPOW_MORE).
+ * and so were the scan (dpow_scan, dpow_scan_slice, DPOW_MORE) and the census
+ * (dpow_census_window, dpow_census_merge).
  * A consumer built against another version must refuse the library before any
  * other call (distpow/_lib.py check_abi, tests/c/abi_harness.c). */
 #define DPOW_ABI_VERSION 5
@@ -202,6 +203,60 @@ int dpow_scan(dpow_ctx *ctx, const uint8_t *nonce, size_t nonce_len, uint32_t nt
               dpow_scan_hit *out, size_t max_hits, size_t *n_hits, uint64_t *k_done,
               dpow_batch_stats *stats /* may be NULL */);
 /* (dpow_scan_slice, the scan's slice rule, is with the host helpers below.) */
+
+/* ---------------------------------------------------------------------------
+ * Census (added within ABI 5): depth counts and per-depth first hits of a window in one pass.
+ *
+ * A search answers "the first hit at depth N", a scan "which candidates reach depth N".  A census
+ * answers "how deep does this window go": over partition (worker_byte, worker_bits) and k in
+ * [k_begin, k_end), a candidate's depth being the trailing '0' characters of its digest (0..32),
+ * for every d in 0..32
+ *   count_ge[d]  the number of candidates with depth >= d (count_ge[0]: the window's size);
+ *   first_ge[d]  the lowest global index with depth >= d, or DPOW_NONE: what dpow_search with
+ *                ntz = d returns for the window (first_ge[0]: the window's first candidate);
+ *   first_tz[d]  that candidate's depth by the host MD5 (0 where first_ge[d] is DPOW_NONE);
+ * and deepest, the largest d with count_ge[d] > 0: first_ge[deepest] is the deepest candidate,
+ * ties going to the lowest index.  Of an empty window count_ge is all 0, first_ge all DPOW_NONE
+ * and deepest 0.  It is what a cache that keeps a nonce's dominant secret, a difficulty
+ * calibration, an audit or best-share mining under a hash budget asks, without an ntz chosen up
+ * front and without a list: the answer is 33 counts and 33 indices whatever the density.
+ *
+ * One generic kernel (csrc/md5_census.hip) counts one bounded launch per 2^28 local indices of
+ * the window; the host checks each launch's table, recomputes every first
+ * index with the host MD5 (a failure is DPOW_EVERIFY) and folds it with dpow_census_merge's code.
+ *
+ * dpow_census_window returns DPOW_EXHAUSTED (0): the window is done, *k_done = k_end.
+ * DPOW_CANCELLED: the context's cancel flag is raised (checked on entry, where it costs no launch
+ * and leaves *k_done = k_begin, and between launches); *out is the complete census of
+ * [k_begin, *k_done), and the caller continues from *k_done and merges.  The argument errors are
+ * dpow_scan's, returned before any GPU work: DPOW_EINVAL for a NULL pointer (stats may be NULL),
+ * worker_byte > 255, k_begin > k_end, a nonce longer than DPOW_MAX_NONCE or a context with a node
+ * slot attached; DPOW_ERANGE for k_end > DPOW_K_LIMIT.  An empty window is DPOW_EXHAUSTED without
+ * a launch.  One search, batch, scan or census is in flight per context.  dpow_search_bound has
+ * no effect on a census, and a census does not touch dpow_stats: its counts go to *stats.
+ *
+ * dpow_census_merge is a pure host function (no context, no GPU): it folds into `into` the census
+ * `next` of a window that lies wholly above into's.  Counts add; for each depth first_ge and
+ * first_tz keep into's entry unless it is DPOW_NONE; deepest is the maximum.  Returns 0, or
+ * DPOW_EINVAL with `into` unchanged when an argument is NULL or not self-consistent -- count_ge
+ * does not increase with d, count_ge[d] > 0 exactly where first_ge[d] is set, the set first_ge do
+ * not decrease with d, first_tz[d] >= d where set, deepest as defined above -- or when a set
+ * first_ge of next is not above every set first_ge of into.
+ * ------------------------------------------------------------------------- */
+#define DPOW_CENSUS_DEPTHS 33
+#define DPOW_NONE DPOW_NO_HIT   /* an absent index of a census */
+typedef struct dpow_census {
+    uint64_t count_ge[DPOW_CENSUS_DEPTHS];
+    uint64_t first_ge[DPOW_CENSUS_DEPTHS];
+    uint32_t first_tz[DPOW_CENSUS_DEPTHS];
+    uint32_t deepest;
+} dpow_census;
+int dpow_census_window(dpow_ctx *ctx, const uint8_t *nonce, size_t nonce_len,
+                       uint32_t worker_byte, uint32_t worker_bits,
+                       uint64_t k_begin, uint64_t k_end,
+                       dpow_census *out, uint64_t *k_done,
+                       dpow_batch_stats *stats /* may be NULL */);
+int dpow_census_merge(dpow_census *into, const dpow_census *next);
 
 /* ---------------------------------------------------------------------------
  * Task queue (added within ABI 5): the batched search as a service on one GPU.

@@ -31,6 +31,9 @@
 #                    queue_rate.json)
 #   scan [reps]      the scan's GPU tests, then its rate beside batch_kernel's, the walk against the scan
 #                    and the dense cost (tools/scan_rate.py -> scan_rate.json)
+#   census [reps] [n=lib.so ...]   the census's GPU tests, then its rate beside scan_kernel's, the dense window and
+#                    a fixture window beside the scan (tools/census_rate.py -> census_rate.json); n=lib.so:
+#                    libraries built with EXTRA=-DDPOW_CENSUS_RARE=n, for the kCensusRare comparison
 set -o pipefail
 task=${1:?task}; tag=${2:?tag}; shift 2
 out=gpurun_out/$tag
@@ -120,6 +123,12 @@ scan)
     timeout -k 10 300 python3 -u -m pytest tests/test_gpu_scan.py -m gpu -x -v -s > $out/pytest_scan.txt 2>&1 &&
     timeout -k 10 300 python3 -u tools/scan_rate.py --reps "${1:-5}" --out $out/scan_rate.json \
         > $out/scan_rate.txt 2> $out/scan_rate.err ;;
+census)
+    reps=${1:-5}; [ $# -gt 0 ] && shift
+    rare=(); for spec in "$@"; do rare+=(--rare "$spec"); done
+    timeout -k 10 300 python3 -u -m pytest tests/test_gpu_census.py -m gpu -x -v -s > $out/pytest_census.txt 2>&1 &&
+    timeout -k 10 300 python3 -u tools/census_rate.py --reps "$reps" --out $out/census_rate.json "${rare[@]}" \
+        > $out/census_rate.txt 2> $out/census_rate.err ;;
 ab) timeout -k 10 800 python3 -u tools/ab_variants.py "$@" > $out/ab.log 2>&1 ;;
 node-ab)
     runs=$1; shift

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Device-only disassembly of every kernel translation unit of libdpow.so (the 8 (NBLK, SH) units,
-# the 2 chunk-length-spanning units, the segment-inner unit, search_ctrl.hip, the batch and the scan unit), one .s per unit, into DIR: a refactor of
+# the 2 chunk-length-spanning units, the segment-inner unit, search_ctrl.hip, the batch, the scan and the census unit), one .s per unit, into DIR: a refactor of
 # the kernel sources that claims to change nothing is checked by diffing two dumps.
 #   bash tools/isa_dump.sh DIR [extra hipcc flags]
 set -e
@@ -26,4 +26,5 @@ unit si1_0 md5_variant.hip -DDPOW_VSI=1 -DDPOW_VNBLK=1 -DDPOW_VSH=0 "$@" &
 unit ctrl search_ctrl.hip "$@" &
 unit batch md5_batch.hip "$@" &  # batch_kernel, queue_kernel and their upload kernels
 unit scan md5_scan.hip "$@" &    # scan_kernel
+unit census md5_census.hip "$@" &  # census_kernel
 wait
