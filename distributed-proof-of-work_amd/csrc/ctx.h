@@ -135,6 +135,7 @@ struct LaunchSlot {
 struct BatchState;  // batch.h
 struct ScanState;   // scan.h
 struct CensusState;  // census.h
+struct DigestState;  // digests.h
 
 // The body of dpow_search (arguments checked): search.cpp.
 int search_window(dpow_ctx *c, const uint8_t *nonce, size_t nonce_len, uint32_t ntz, uint32_t worker_byte,
@@ -201,6 +202,7 @@ struct __attribute__((visibility("default"))) dpow_ctx {
     dpow::BatchState *batch = nullptr;  // buffers of dpow_search_batch: allocated by the first batch (batch.cpp)
     dpow::ScanState *scan = nullptr;    // buffers of dpow_scan: allocated by the first scan (scan.cpp)
     dpow::CensusState *census = nullptr;  // buffers of dpow_census_window: allocated by the first census (census.cpp)
+    dpow::DigestState *digests = nullptr;  // buffers of dpow_digests: allocated by the first call (digests.cpp)
 };
 
 namespace dpow {

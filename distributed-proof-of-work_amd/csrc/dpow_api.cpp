@@ -1,7 +1,7 @@
 // dpow_api.cpp -- the C ABI (include/dpow.h) over the gfx950 search kernels: the context's
 // lifecycle (dpow_open, dpow_close), its accessors and stats, the argument-checking entry points
 // of the searches (dpow_search: search.cpp; dpow_search_batch: batch.cpp; dpow_scan: scan.cpp;
-// dpow_census_window: census.cpp; dpow_search_bound) and the pure host helpers.  The node layer is node.cpp, the dpow_diag_* entry points diag.cpp.
+// dpow_census_window: census.cpp; dpow_digests, dpow_digests_device: digests.cpp; dpow_search_bound) and the pure host helpers.  The node layer is node.cpp, the dpow_diag_* entry points diag.cpp.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -9,10 +9,12 @@
 
 #include <algorithm>
 
+#include "../../include/dpow_worker.h"
 #include "batch.h"
 #include "batch_engine.h"
 #include "census.h"
 #include "ctx.h"
+#include "digests.h"
 #include "md5_host.h"
 #include "md5_variants.h"
 #include "scan.h"
@@ -181,6 +183,7 @@ void dpow_close(dpow_ctx *c) {
     batch_free(c->batch);
     scan_free(c->scan);
     census_free(c->census);
+    digests_free(c->digests);
     if (c->d_ctrl_alloc) (void)hipFree(c->d_ctrl_alloc);
     if (c->d_claims) (void)hipFree(c->d_claims);
     if (c->h_snap) (void)hipHostFree(c->h_snap);
@@ -334,6 +337,51 @@ int dpow_census_window(dpow_ctx *c, const uint8_t *nonce, size_t nonce_len, uint
     c->last_use.store(now_ns(), std::memory_order_relaxed);
     return census_run(&c->census, c->stream, c->h_cancel, nonce, nonce_len, worker_byte, worker_bits, k_begin, k_end,
                       out, k_done, stats);
+}
+
+// The argument errors dpow_digests and dpow_digests_device share (`who`: the entry point named in the message).
+static int digests_check(dpow_ctx *c, const uint8_t *nonce, size_t nonce_len, const void *idx, const void *digest_out,
+                         const void *tz_out, const char *who) {
+    const std::string w(who);
+    if (!c || !idx) return set_error(DPOW_EINVAL, w + ": NULL argument");
+    if (!digest_out && !tz_out) return set_error(DPOW_EINVAL, w + ": both outputs are NULL");
+    if (nonce_len && !nonce) return set_error(DPOW_EINVAL, w + ": nonce is NULL");
+    if (nonce_len > DPOW_MAX_NONCE) return set_error(DPOW_EINVAL, w + ": nonce longer than DPOW_MAX_NONCE");
+    if (c->node) return set_error(DPOW_EINVAL, w + ": a node slot is attached to the context");
+    return 0;
+}
+
+int dpow_digests(dpow_ctx *c, const uint8_t *nonce, size_t nonce_len, const uint64_t *global_idx, size_t n,
+                 uint8_t *digest_out, uint8_t *tz_out, size_t *n_done, dpow_batch_stats *stats) {
+    if (!n_done) return set_error(DPOW_EINVAL, "dpow_digests: NULL argument");
+    const int rc = digests_check(c, nonce, nonce_len, global_idx, digest_out, tz_out, "dpow_digests");
+    if (rc < 0) return rc;
+    for (size_t j = 0; j < n; ++j)
+        if ((global_idx[j] >> 8) >= DPOW_K_LIMIT)
+            return set_error(DPOW_ERANGE, "dpow_digests: an entry beyond DPOW_K_LIMIT");
+    *n_done = 0;
+    if (stats) *stats = dpow_batch_stats{};
+    if (n == 0) return DPOW_EXHAUSTED;
+    if (__atomic_load_n(c->h_cancel, __ATOMIC_ACQUIRE) != 0u) return DPOW_CANCELLED;  // raised on entry: no launch
+    const DeviceScope on_device(c->device);
+    if (on_device.e != hipSuccess) return hip_fail(on_device.e, "hipSetDevice");
+    c->last_use.store(now_ns(), std::memory_order_relaxed);
+    return digests_run(&c->digests, c->stream, c->h_cancel, nonce, nonce_len, global_idx, n, digest_out, tz_out, n_done,
+                       stats);
+}
+
+int dpow_digests_device(dpow_ctx *c, const uint8_t *nonce, size_t nonce_len, const void *d_global_idx, size_t n,
+                        void *d_digest_out, void *d_tz_out, dpow_batch_stats *stats) {
+    const int rc = digests_check(c, nonce, nonce_len, d_global_idx, d_digest_out, d_tz_out, "dpow_digests_device");
+    if (rc < 0) return rc;
+    if ((reinterpret_cast<uintptr_t>(d_global_idx) & 7u) != 0u || (reinterpret_cast<uintptr_t>(d_digest_out) & 15u) != 0u)
+        return set_error(DPOW_EINVAL, "dpow_digests_device: indices not 8-byte or digests not 16-byte aligned");
+    if (stats) *stats = dpow_batch_stats{};
+    if (n == 0) return DPOW_EXHAUSTED;
+    const DeviceScope on_device(c->device);
+    if (on_device.e != hipSuccess) return hip_fail(on_device.e, "hipSetDevice");
+    c->last_use.store(now_ns(), std::memory_order_relaxed);
+    return digests_run_device(&c->digests, c->stream, nonce, nonce_len, d_global_idx, n, d_digest_out, d_tz_out, stats);
 }
 
 int dpow_search(dpow_ctx *c, const uint8_t *nonce, size_t nonce_len, uint32_t ntz, uint32_t worker_byte,

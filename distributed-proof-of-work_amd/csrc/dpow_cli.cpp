@@ -19,6 +19,12 @@
 //       how deep the window goes (dpow_census_window), one line per depth up to the deepest: the
 //       depth, the number of candidates at least that deep, the first one's global index and its
 //       secret in hex
+//   dpow_cli digest <nonce-hex> <idx> [idx ...] [--device N]
+//       the MD5 and the depth of the listed global indices (dpow_digests), one line per entry: its
+//       index, its depth, its secret in hex and its md5 in hex
+//   dpow_cli digest-host <nonce-hex> <log2-n> [reps]
+//       time dpow_digest_of_index in a loop over 2^n sequential indices from 2^32 (no GPU): what a
+//       caller pays per entry on the host; one JSON line with the median of `reps` loops
 // Each other command prints one JSON line.
 #include <stdio.h>
 #include <stdlib.h>
@@ -296,7 +302,67 @@ static int cmd_census(int argc, char **argv) {
     return rc == DPOW_EXHAUSTED ? 0 : 1;
 }
 
+static int cmd_digest(int argc, char **argv) {
+    if (argc < 4) return 2;
+    std::vector<uint8_t> nonce = from_hex(argv[2]);
+    int dev = 0;
+    std::vector<uint64_t> idx;
+    for (int i = 3; i < argc; ++i) {
+        if (!strcmp(argv[i], "--device") && i + 1 < argc) dev = atoi(argv[++i]);
+        else idx.push_back(strtoull(argv[i], nullptr, 0));
+    }
+    if (idx.empty()) return 2;
+    dpow_ctx *ctx = nullptr;
+    int rc = dpow_open(dev, &ctx);
+    if (rc) return fail("dpow_open", rc);
+    std::vector<uint8_t> digest(16 * idx.size()), tz(idx.size());
+    size_t n_done = 0;
+    rc = dpow_digests(ctx, nonce.data(), nonce.size(), idx.data(), idx.size(), digest.data(), tz.data(), &n_done,
+                      nullptr);
+    if (rc < 0) return fail("dpow_digests", rc);
+    for (size_t i = 0; i < n_done; ++i) {
+        uint8_t sec[DPOW_MAX_SECRET];
+        size_t len = 0;
+        dpow_secret_from_index(idx[i], sec, &len);
+        printf("%llu %u ", (unsigned long long)idx[i], tz[i]);
+        for (size_t b = 0; b < len; ++b) printf("%02x", sec[b]);
+        printf(" ");
+        for (size_t b = 0; b < 16; ++b) printf("%02x", digest[16 * i + b]);
+        printf("\n");
+    }
+    dpow_close(ctx);
+    return rc == DPOW_EXHAUSTED ? 0 : 1;
+}
+
+static int cmd_digest_host(int argc, char **argv) {
+    if (argc < 4) return 2;
+    std::vector<uint8_t> nonce = from_hex(argv[2]);
+    const int lg = atoi(argv[3]);
+    const int reps = argc > 4 ? atoi(argv[4]) : 5;
+    if (lg < 0 || lg > 26 || reps < 1) return 2;
+    const uint64_t n = 1ull << lg, g0 = 1ull << 32;
+    std::vector<double> ns;
+    uint32_t sink = 0;
+    for (int r = 0; r < reps + 1; ++r) {  // (the first loop is the warm-up)
+        const double t0 = now_s();
+        for (uint64_t j = 0; j < n; ++j) {
+            uint8_t d[16];
+            uint32_t tz = 0;
+            const int rc = dpow_digest_of_index(nonce.data(), nonce.size(), g0 + j, d, &tz);
+            if (rc < 0) return fail("dpow_digest_of_index", rc);
+            sink += tz + d[0];
+        }
+        if (r) ns.push_back((now_s() - t0) * 1e9 / (double)n);
+    }
+    std::sort(ns.begin(), ns.end());
+    printf("{\"n\":%llu,\"ns_per_entry\":%.2f,\"call_ms\":%.4f,\"sink\":%u}\n", (unsigned long long)n,
+           ns[ns.size() / 2], ns[ns.size() / 2] * (double)n * 1e-6, sink);
+    return 0;
+}
+
 int main(int argc, char **argv) {
+    if (argc >= 2 && !strcmp(argv[1], "digest")) return cmd_digest(argc, argv);
+    if (argc >= 2 && !strcmp(argv[1], "digest-host")) return cmd_digest_host(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "census")) return cmd_census(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "scan")) return cmd_scan(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "batch")) return cmd_batch(argc, argv);
@@ -311,6 +377,8 @@ int main(int argc, char **argv) {
             "       dpow_cli latency [reps [device]]\n"
             "       dpow_cli batch <ntz> <nonce-hex> [<nonce-hex> ...] [--device N]\n"
             "       dpow_cli scan <nonce-hex> <ntz> <k_begin> <k_end> [worker_byte worker_bits [device]]\n"
-            "       dpow_cli census <nonce-hex> <k_begin> <k_end> [worker_byte worker_bits [device]]\n");
+            "       dpow_cli census <nonce-hex> <k_begin> <k_end> [worker_byte worker_bits [device]]\n"
+            "       dpow_cli digest <nonce-hex> <idx> [idx ...] [--device N]\n"
+            "       dpow_cli digest-host <nonce-hex> <log2-n> [reps]\n");
     return 2;
 }

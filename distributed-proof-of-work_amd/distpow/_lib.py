@@ -103,6 +103,8 @@ class ScanHitC(ctypes.Structure):
                 ("secret", ctypes.c_uint8 * DPOW_MAX_SECRET)]
 
 
+DIGEST_BAD_DEPTH = 0xFF  # dpow_digests_device: the depth byte of an entry beyond DPOW_K_LIMIT
+
 CENSUS_DEPTHS = 33  # depths 0..32 (include/dpow.h DPOW_CENSUS_DEPTHS)
 
 
@@ -293,6 +295,11 @@ def lib():
                                               ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(CensusC), u64p,
                                               ctypes.POINTER(BatchStats)]),
         "dpow_census_merge": (ctypes.c_int, [ctypes.POINTER(CensusC), ctypes.POINTER(CensusC)]),
+        "dpow_digests": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_size_t, vp, ctypes.c_size_t, vp, vp, szp,
+                                        ctypes.POINTER(BatchStats)]),
+        "dpow_digests_device": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_size_t, vp, ctypes.c_size_t, vp, vp,
+                                               ctypes.POINTER(BatchStats)]),
+        "dpow_digest_of_index": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint64, u8p, u32p]),
         "dpow_queue_open": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(vp)]),
         "dpow_queue_close": (None, [vp]),
         "dpow_queue_submit": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32,

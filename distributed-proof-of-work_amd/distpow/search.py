@@ -6,6 +6,7 @@ sequence of GPU windows; `Miner.search` is one window (the C ABI dpow_search).
 Names and argument meaning follow the reference: nonce, num_trailing_zeros
 (NumTrailingZeros), worker_byte (WorkerByte), worker_bits (WorkerBits).
 """
+import array
 import ctypes
 import struct
 from dataclasses import dataclass
@@ -17,7 +18,7 @@ from ._lib import (CANCELLED, DPOW_K_LIMIT, DPOW_MAX_SECRET, DPOW_NO_HIT, EXHAUS
 
 __all__ = ["Miner", "SearchResult", "BatchTask", "batch_candidate", "batch_plan", "batch_plan_block",
            "TaskQueue", "QueueResult", "queue_plan", "ScanHit", "scan_slice", "Census",
-           "secret_from_index", "md5", "verify", "trailing_zero_nibbles",
+           "digest_of_index", "secret_from_index", "md5", "verify", "trailing_zero_nibbles",
            "thread_bytes", "remainder_bits", "global_index", "plan_window", "plan_candidate",
            "device_count", "DPOW_NO_HIT", "FOUND", "EXHAUSTED", "CANCELLED"]
 
@@ -64,6 +65,15 @@ def md5(msg) -> bytes:
     m = _b(msg)
     lib().dpow_md5(m, len(m), out)
     return bytes(out)
+
+
+def digest_of_index(nonce, global_idx: int):
+    """(digest, depth) of one candidate on the host (dpow_digest_of_index): the 16-byte MD5 of
+    nonce || secret_from_index(global_idx) and its trailing '0' characters."""
+    n = _b(nonce)
+    out, tz = (ctypes.c_uint8 * 16)(), ctypes.c_uint32()
+    check(lib().dpow_digest_of_index(n, len(n), global_idx, out, ctypes.byref(tz)), "dpow_digest_of_index")
+    return bytes(out), tz.value
 
 
 def trailing_zero_nibbles(digest: bytes) -> int:
@@ -491,6 +501,76 @@ class Miner:
         (dpow_census_window).  A raised cancel flag ends it early with the census of the part done
         (see `cancelled`; census_page tells how far it got)."""
         return self.census_page(nonce, worker_byte, worker_bits, k_begin, k_end)[1]
+
+    # -- digests ----------------------------------------------------------------
+    @staticmethod
+    def _u64_list(indices):
+        """(keep-alive object, address, n) of a list of global indices: a sequence of ints, or any
+        contiguous buffer of 8-byte items (array('Q'), a uint64 array, packed little-endian bytes)."""
+        try:
+            mv = memoryview(indices)
+        except TypeError:
+            mv = memoryview(array.array("Q", indices))
+        if not mv.contiguous or (mv.itemsize != 8 and (mv.itemsize != 1 or mv.nbytes % 8)):
+            raise ValueError("digests: indices must be ints or a contiguous buffer of uint64")
+        n = mv.nbytes // 8
+        if n == 0:
+            return None, None, 0
+        raw = mv.cast("B")
+        buf = (ctypes.c_uint8 * raw.nbytes).from_buffer_copy(raw) if raw.readonly else \
+            (ctypes.c_uint8 * raw.nbytes).from_buffer(raw)
+        return buf, ctypes.addressof(buf), n
+
+    def digests(self, nonce: Sequence[int], indices, want_digests: bool = True, want_depths: bool = True):
+        """(digests, depths) of the listed candidates of one nonce (dpow_digests): 16 bytes and one
+        byte per entry, in the list's order -- the MD5 of nonce || secret_from_index(g) and its
+        trailing '0' characters.  `indices` is a sequence of ints or any buffer of uint64, in any
+        order, duplicates included.  An output not wanted is None.  A raised cancel flag ends the call
+        early with the entries done so far (shorter outputs; last_digest_status is CANCELLED).  The
+        call's launch counts are kept in last_digest_stats."""
+        nb = _b(nonce)
+        keep, addr, n = self._u64_list(indices)
+        dig = ctypes.create_string_buffer(16 * n) if want_digests else None
+        dep = ctypes.create_string_buffer(max(n, 1)) if want_depths else None
+        done, st = ctypes.c_size_t(), _lib.BatchStats()
+        if n == 0:  # (an empty list still goes through the call's argument checks)
+            keep = ctypes.c_uint64()
+            addr = ctypes.addressof(keep)
+        r = check(lib().dpow_digests(self._ctx, nb, len(nb), addr, n, dig, dep, ctypes.byref(done), ctypes.byref(st)),
+                  "dpow_digests")
+        del keep
+        self.last_digest_stats, self.last_digest_status = st, r
+        m = done.value
+        return (dig.raw[:16 * m] if want_digests else None, dep.raw[:m] if want_depths else None)
+
+    def digests_cuda(self, nonce: Sequence[int], idx, strict: bool = True):
+        """`digests` for a CUDA torch.int64 tensor of global indices on this context's device
+        (dpow_digests_device): uint8 tensors of shape [n, 16] and [n] on the same device, nothing
+        crossing to the host.  torch's current stream is synchronised before the call, and the outputs
+        are complete on return.  The device cannot refuse a list up front: an entry beyond DPOW_K_LIMIT
+        (a negative one included) reads depth 255 and a zero digest, and the call raises DpowError with
+        code ERANGE -- or, with strict=False, returns the outputs so marked."""
+        import torch
+        if not (isinstance(idx, torch.Tensor) and idx.is_cuda and idx.dtype == torch.int64 and idx.dim() == 1):
+            raise ValueError("digests_cuda: idx must be a one-dimensional CUDA torch.int64 tensor")
+        if idx.device.index != self.device:
+            raise ValueError(f"digests_cuda: idx is on {idx.device}, the context on device {self.device}")
+        nb = _b(nonce)
+        idx = idx.contiguous()
+        n = idx.numel()
+        dig = torch.empty((n, 16), dtype=torch.uint8, device=idx.device)
+        dep = torch.empty((n,), dtype=torch.uint8, device=idx.device)
+        st = _lib.BatchStats()
+        self.last_digest_stats, self.last_digest_status = st, EXHAUSTED
+        if n == 0:
+            return dig, dep
+        torch.cuda.current_stream(idx.device).synchronize()
+        r = lib().dpow_digests_device(self._ctx, nb, len(nb), idx.data_ptr(), n, dig.data_ptr(), dep.data_ptr(),
+                                      ctypes.byref(st))
+        self.last_digest_status = r
+        if not (r == _lib.ERANGE and not strict):
+            check(r, "dpow_digests_device")
+        return dig, dep
 
     # -- measurement ------------------------------------------------------------
     def stats(self) -> Stats:

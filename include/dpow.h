@@ -36,7 +36,8 @@ extern "C" {
  * refuses a library that lacks a prototype it lists, or one built from another tree.
  * The task queue (dpow_queue_*, DPOW_EAGAIN) and dpow_worker_set_queue were added the same way,
  * and so were the scan (dpow_scan, dpow_scan_slice, DPOW_MORE) and the census
- * (dpow_census_window, dpow_census_merge).
+ * (dpow_census_window, dpow_census_merge) and the digests (dpow_digests, dpow_digests_device,
+ * dpow_digest_of_index).
  * A consumer built against another version must refuse the library before any
  * other call (distpow/_lib.py check_abi, tests/c/abi_harness.c). */
 #define DPOW_ABI_VERSION 5
@@ -257,6 +258,64 @@ int dpow_census_window(dpow_ctx *ctx, const uint8_t *nonce, size_t nonce_len,
                        dpow_census *out, uint64_t *k_done,
                        dpow_batch_stats *stats /* may be NULL */);
 int dpow_census_merge(dpow_census *into, const dpow_census *next);
+
+/* ---------------------------------------------------------------------------
+ * Digests (added within ABI 5): MD5 and depth of any listed candidates in one pass.
+ *
+ * Every call above walks a contiguous window and reports the candidates whose digest ends in
+ * zeros.  dpow_digests takes a list of global indices of one nonce and returns what the GPU
+ * computes for each: entry j of digest_out is the 16-byte MD5 of
+ * nonce || dpow_secret_from_index(global_idx[j]) and entry j of tz_out its depth, the trailing '0'
+ * characters of its hex form (0..32).  A global index fixes the secret, so there is no partition
+ * argument.  The list may be in any order and duplicates are legal; outputs are positional; either
+ * output may be NULL, not both.  It is what a pool checking the shares a scan produced, a cache
+ * audit, or a client re-checking a census's first_ge asks, instead of one host MD5 per entry.
+ *
+ * One generic kernel (csrc/md5_digest.hip) hashes the list in chunks of 2^18 entries, one launch
+ * each, staged through two buffer sets so that chunk i + 1's indices move while chunk i hashes
+ * (DESIGN.md section 15); device memory does not grow with n.
+ *
+ * Verification is sampled: re-hashing every entry on the host would cost what the call saves.  Of
+ * each chunk the host recomputes the first entry, the last entry and 14 evenly spaced ones
+ * (dpow_digest_of_index) and compares every output asked for; a mismatch is DPOW_EVERIFY.  A
+ * caller that needs every entry host-verified calls dpow_digest_of_index itself.
+ *
+ * Returns DPOW_EXHAUSTED (0): the list is done, *n_done = n.  DPOW_CANCELLED: the context's cancel
+ * flag is raised (checked on entry, where it costs no launch, and between chunks); entries
+ * [0, *n_done) of the outputs are complete.  Argument errors are returned before any GPU work
+ * with the outputs untouched: DPOW_EINVAL for a NULL ctx, global_idx or n_done (stats may be
+ * NULL), both outputs NULL, a NULL nonce with a non-zero nonce_len, a nonce longer than
+ * DPOW_MAX_NONCE or a context with a node slot attached; DPOW_ERANGE for any entry g with
+ * (g >> 8) >= DPOW_K_LIMIT.  n = 0 returns 0 without a launch.  One search, batch, scan, census
+ * or digest call is in flight per context.  The call does not touch dpow_stats: stats->candidates
+ * = the entries done, stats->launches = the chunks, stats->kernel_ms = the launches' durations.
+ *
+ * dpow_digests_device is the same kernel on lists already in device memory: d_global_idx holds n
+ * uint64 (8-byte aligned), d_digest_out 16 n bytes (16-byte aligned), d_tz_out n bytes; either
+ * output may be NULL, not both.  The caller guarantees the inputs are ready (the work that
+ * produced them has completed); the function returns after the context's stream has drained, so
+ * the outputs are complete on return.  It cannot pre-check the list: the kernel writes the depth
+ * byte 0xFF and a zero digest for an entry with (g >> 8) >= DPOW_K_LIMIT and counts such entries
+ * in a device word, and the function returns DPOW_ERANGE if that count is not zero -- the valid
+ * entries are written all the same.  It verifies nothing, because the data never reaches the
+ * host, and it does not look at the cancel flag (one bounded launch per 2^24 entries).  The other
+ * argument errors are dpow_digests', plus DPOW_EINVAL for a misaligned pointer.
+ *
+ * dpow_digest_of_index is the pure host counterpart (no context, no GPU): dpow_secret_from_index
+ * plus the host MD5.  Either output may be NULL, not both (DPOW_EINVAL); DPOW_EINVAL for a NULL
+ * nonce with a non-zero nonce_len, DPOW_ERANGE for (global_idx >> 8) >= DPOW_K_LIMIT.
+ * ------------------------------------------------------------------------- */
+int dpow_digests(dpow_ctx *ctx, const uint8_t *nonce, size_t nonce_len,
+                 const uint64_t *global_idx, size_t n,
+                 uint8_t *digest_out /* 16 n bytes, may be NULL */,
+                 uint8_t *tz_out     /* n bytes, may be NULL */,
+                 size_t *n_done, dpow_batch_stats *stats /* may be NULL */);
+int dpow_digests_device(dpow_ctx *ctx, const uint8_t *nonce, size_t nonce_len,
+                        const void *d_global_idx, size_t n,
+                        void *d_digest_out, void *d_tz_out,
+                        dpow_batch_stats *stats /* may be NULL */);
+int dpow_digest_of_index(const uint8_t *nonce, size_t nonce_len, uint64_t global_idx,
+                         uint8_t digest_out[16], uint32_t *tz_out);   /* pure host */
 
 /* ---------------------------------------------------------------------------
  * Task queue (added within ABI 5): the batched search as a service on one GPU.

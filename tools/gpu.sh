@@ -34,6 +34,9 @@
 #   census [reps] [n=lib.so ...]   the census's GPU tests, then its rate beside scan_kernel's, the dense window and
 #                    a fixture window beside the scan (tools/census_rate.py -> census_rate.json); n=lib.so:
 #                    libraries built with EXTRA=-DDPOW_CENSUS_RARE=n, for the kCensusRare comparison
+#   digest [reps] [chunk-lib.so]   the digests' GPU tests, then the kernel's rate beside scan_kernel's, the host
+#                    call beside the host loops, the two stagings and the chunk sizes (tools/digest_rate.py ->
+#                    digest_rate.json); chunk-lib.so: a library built with EXTRA=-DDPOW_DIGEST_CHUNK_LOG2=20
 set -o pipefail
 task=${1:?task}; tag=${2:?tag}; shift 2
 out=gpurun_out/$tag
@@ -129,6 +132,12 @@ census)
     timeout -k 10 300 python3 -u -m pytest tests/test_gpu_census.py -m gpu -x -v -s > $out/pytest_census.txt 2>&1 &&
     timeout -k 10 300 python3 -u tools/census_rate.py --reps "$reps" --out $out/census_rate.json "${rare[@]}" \
         > $out/census_rate.txt 2> $out/census_rate.err ;;
+digest)
+    reps=${1:-5}; lib=()
+    [ -n "$2" ] && lib=(--chunk-lib "$2")
+    timeout -k 10 300 python3 -u -m pytest tests/test_gpu_digests.py -m gpu -x -v -s > $out/pytest_digests.txt 2>&1 &&
+    timeout -k 10 500 python3 -u tools/digest_rate.py --reps "$reps" --out $out/digest_rate.json "${lib[@]}" \
+        > $out/digest_rate.txt 2> $out/digest_rate.err ;;
 ab) timeout -k 10 800 python3 -u tools/ab_variants.py "$@" > $out/ab.log 2>&1 ;;
 node-ab)
     runs=$1; shift
