@@ -12,6 +12,7 @@
 
 #include <string.h>
 
+#include <string>
 #include <vector>
 
 #include "../../include/dpow_worker.h"
@@ -66,6 +67,53 @@ bool census_merge(dpow_census &into, const dpow_census &next) {
 }
 
 }  // namespace
+
+// One launch's table folded into `into`: the launch covered the local indices [lo, hi) of a task
+// with partition (rbits, base_tb); cnt and first are its 33 counts and 33 indices as the kernel left
+// them in pinned memory.  Depth 0 (the launch's size and its first candidate) is the host's own.
+// The table is checked -- no more counted than hashed, every first index a candidate of this
+// launch's range and partition -- each distinct first index is recomputed with the host MD5, which
+// is where first_tz comes from, and the launch is folded with the code of dpow_census_merge.  `msg`
+// holds the task's nonce (nonce_len bytes) in front of DPOW_MAX_SECRET free bytes.  0, or
+// DPOW_EVERIFY with "`who`: ..." set.
+int census_fold_launch(const char *who, uint8_t *msg, size_t nonce_len, uint32_t rbits, uint32_t base_tb, uint64_t lo,
+                       uint64_t hi, const unsigned long long *cnt, const unsigned long long *first, dpow_census &into) {
+    const std::string w(who);
+    dpow_census one;
+    census_clear(one);
+    one.count_ge[0] = hi - lo;
+    one.first_ge[0] = global_of_local(lo, rbits, base_tb);
+    for (uint32_t d = 1; d < kCensusDepths; ++d) {
+        one.count_ge[d] = cnt[d];
+        one.first_ge[d] = first[d];
+    }
+    if (one.count_ge[1] > hi - lo) return set_error(DPOW_EVERIFY, w + ": more candidates counted than hashed");
+    for (uint32_t d = 0; d < kCensusDepths; ++d) {
+        const uint64_t g = one.first_ge[d];
+        if (g == DPOW_NO_HIT) continue;
+        // The index is a candidate of this launch's range and partition.
+        const uint32_t tb = (uint32_t)(g & 255u);
+        const uint64_t i = ((g >> 8) << rbits) | (tb & ((1u << rbits) - 1u));
+        if ((tb >> rbits) != (base_tb >> rbits) || i < lo || i >= hi)
+            return set_error(DPOW_EVERIFY, w + ": kernel index outside its launch");
+        if (d > 0 && g == one.first_ge[d - 1]) {
+            one.first_tz[d] = one.first_tz[d - 1];
+        } else {
+            uint8_t sec[DPOW_MAX_SECRET], dig[16];
+            size_t len = 0;
+            dpow_secret_from_index(g, sec, &len);
+            memcpy(msg + nonce_len, sec, len);
+            md5_digest(msg, nonce_len + len, dig);
+            one.first_tz[d] = digest_trailing_zero_nibbles(dig);
+        }
+        if (one.first_tz[d] < d) return set_error(DPOW_EVERIFY, w + ": kernel index failed host MD5 verification");
+        one.deepest = d;
+    }
+    // (census_merge checks both sides: the launch's table is self-consistent, or it is refused.)
+    if (!census_merge(into, one))
+        return set_error(DPOW_EVERIFY, w + ": the launch's counts and indices contradict each other");
+    return 0;
+}
 
 // The context's buffers.  Device: the launch's table (cnt[33], first[33]) in the engine's image
 // area, the control words behind it (batch_engine.h).  Pinned: the table's copy, the record.
@@ -153,42 +201,8 @@ int census_run(CensusState **state, hipStream_t stream, const volatile uint32_t 
         if (rc < 0) return rc;
         st.candidates += hi - lo;
 
-        // The launch's census: depth 0 from the host, the rest from the table.
-        dpow_census one;
-        census_clear(one);
-        one.count_ge[0] = hi - lo;
-        one.first_ge[0] = global_of_local(lo, rbits, base_tb);
-        for (uint32_t d = 1; d < kCensusDepths; ++d) {
-            one.count_ge[d] = h_cnt[d];
-            one.first_ge[d] = h_first[d];
-        }
-        if (one.count_ge[1] > hi - lo)
-            return set_error(DPOW_EVERIFY, "dpow_census_window: more candidates counted than hashed");
-        for (uint32_t d = 0; d < kCensusDepths; ++d) {
-            const uint64_t g = one.first_ge[d];
-            if (g == DPOW_NO_HIT) continue;
-            // The index is a candidate of this launch's range and partition.
-            const uint32_t tb = (uint32_t)(g & 255u);
-            const uint64_t i = ((g >> 8) << rbits) | (tb & ((1u << rbits) - 1u));
-            if ((tb >> rbits) != (base_tb >> rbits) || i < lo || i >= hi)
-                return set_error(DPOW_EVERIFY, "dpow_census_window: kernel index outside its launch");
-            if (d > 0 && g == one.first_ge[d - 1]) {
-                one.first_tz[d] = one.first_tz[d - 1];
-            } else {
-                uint8_t sec[DPOW_MAX_SECRET], dig[16];
-                size_t len = 0;
-                dpow_secret_from_index(g, sec, &len);
-                memcpy(msg.data() + nonce_len, sec, len);
-                md5_digest(msg.data(), nonce_len + len, dig);
-                one.first_tz[d] = digest_trailing_zero_nibbles(dig);
-            }
-            if (one.first_tz[d] < d)
-                return set_error(DPOW_EVERIFY, "dpow_census_window: kernel index failed host MD5 verification");
-            one.deepest = d;
-        }
-        // (census_merge checks both sides: the launch's table is self-consistent, or it is refused.)
-        if (!census_merge(*out, one))
-            return set_error(DPOW_EVERIFY, "dpow_census_window: the launch's counts and indices contradict each other");
+        rc = census_fold_launch("dpow_census_window", msg.data(), nonce_len, rbits, base_tb, lo, hi, h_cnt, h_first, *out);
+        if (rc < 0) return rc;
         lo = hi;
     }
     return finish(DPOW_EXHAUSTED, k_end);

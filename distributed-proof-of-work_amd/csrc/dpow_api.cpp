@@ -1,7 +1,7 @@
 // dpow_api.cpp -- the C ABI (include/dpow.h) over the gfx950 search kernels: the context's
 // lifecycle (dpow_open, dpow_close), its accessors and stats, the argument-checking entry points
 // of the searches (dpow_search: search.cpp; dpow_search_batch: batch.cpp; dpow_scan: scan.cpp;
-// dpow_census_window: census.cpp; dpow_digests, dpow_digests_device: digests.cpp; dpow_search_bound) and the pure host helpers.  The node layer is node.cpp, the dpow_diag_* entry points diag.cpp.
+// dpow_census_window: census.cpp; dpow_census_batch: census_many.cpp; dpow_digests, dpow_digests_device: digests.cpp; dpow_search_bound) and the pure host helpers.  The node layer is node.cpp, the dpow_diag_* entry points diag.cpp.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -13,6 +13,7 @@
 #include "batch.h"
 #include "batch_engine.h"
 #include "census.h"
+#include "census_many.h"
 #include "ctx.h"
 #include "digests.h"
 #include "md5_host.h"
@@ -183,6 +184,7 @@ void dpow_close(dpow_ctx *c) {
     batch_free(c->batch);
     scan_free(c->scan);
     census_free(c->census);
+    census_many_free(c->census_many);
     digests_free(c->digests);
     if (c->d_ctrl_alloc) (void)hipFree(c->d_ctrl_alloc);
     if (c->d_claims) (void)hipFree(c->d_claims);
@@ -337,6 +339,17 @@ int dpow_census_window(dpow_ctx *c, const uint8_t *nonce, size_t nonce_len, uint
     c->last_use.store(now_ns(), std::memory_order_relaxed);
     return census_run(&c->census, c->stream, c->h_cancel, nonce, nonce_len, worker_byte, worker_bits, k_begin, k_end,
                       out, k_done, stats);
+}
+
+int dpow_census_batch(dpow_ctx *c, dpow_census_task *tasks, size_t n_tasks, dpow_batch_stats *stats) {
+    const int rc = census_many_check(tasks, n_tasks);  // the tasks' own errors first: they need no context
+    if (rc < 0) return rc;
+    if (!c) return set_error(DPOW_EINVAL, "dpow_census_batch: ctx is NULL");
+    if (c->node) return set_error(DPOW_EINVAL, "dpow_census_batch: a node slot is attached to the context");
+    const DeviceScope on_device(c->device);
+    if (on_device.e != hipSuccess) return hip_fail(on_device.e, "hipSetDevice");
+    c->last_use.store(now_ns(), std::memory_order_relaxed);
+    return census_many_run(&c->census_many, c->stream, c->h_cancel, tasks, n_tasks, stats);
 }
 
 // The argument errors dpow_digests and dpow_digests_device share (`who`: the entry point named in the message).

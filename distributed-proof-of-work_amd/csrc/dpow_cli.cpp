@@ -19,6 +19,9 @@
 //       how deep the window goes (dpow_census_window), one line per depth up to the deepest: the
 //       depth, the number of candidates at least that deep, the first one's global index and its
 //       secret in hex
+//   dpow_cli census-many <k_begin> <k_end> <nonce-hex> [<nonce-hex> ...] [--device N]
+//       the census of the same window of every nonce in one batched call (dpow_census_batch): per
+//       task a line "# <nonce-hex>" and then `census`'s lines
 //   dpow_cli digest <nonce-hex> <idx> [idx ...] [--device N]
 //       the MD5 and the depth of the listed global indices (dpow_digests), one line per entry: its
 //       index, its depth, its secret in hex and its md5 in hex
@@ -277,6 +280,18 @@ static int cmd_scan(int argc, char **argv) {
     return rc == DPOW_EXHAUSTED ? 0 : 1;
 }
 
+// One line per depth up to the deepest: the depth, its count, its first index and that secret in hex.
+static void print_census(const dpow_census &c) {
+    for (uint32_t d = 0; d <= c.deepest && c.count_ge[d] > 0; ++d) {
+        uint8_t sec[DPOW_MAX_SECRET];
+        size_t len = 0;
+        dpow_secret_from_index(c.first_ge[d], sec, &len);
+        printf("%u %llu %llu ", d, (unsigned long long)c.count_ge[d], (unsigned long long)c.first_ge[d]);
+        for (size_t b = 0; b < len; ++b) printf("%02x", sec[b]);
+        printf("\n");
+    }
+}
+
 static int cmd_census(int argc, char **argv) {
     if (argc < 5) return 2;
     std::vector<uint8_t> nonce = from_hex(argv[2]);
@@ -290,16 +305,47 @@ static int cmd_census(int argc, char **argv) {
     uint64_t k_done = 0;
     rc = dpow_census_window(ctx, nonce.data(), nonce.size(), wb, wbits, k_begin, k_end, &c, &k_done, nullptr);
     if (rc < 0) return fail("dpow_census_window", rc);
-    for (uint32_t d = 0; d <= c.deepest && c.count_ge[d] > 0; ++d) {
-        uint8_t sec[DPOW_MAX_SECRET];
-        size_t len = 0;
-        dpow_secret_from_index(c.first_ge[d], sec, &len);
-        printf("%u %llu %llu ", d, (unsigned long long)c.count_ge[d], (unsigned long long)c.first_ge[d]);
-        for (size_t b = 0; b < len; ++b) printf("%02x", sec[b]);
-        printf("\n");
-    }
+    print_census(c);
     dpow_close(ctx);
     return rc == DPOW_EXHAUSTED ? 0 : 1;
+}
+
+static int cmd_census_many(int argc, char **argv) {
+    if (argc < 5) return 2;
+    const uint64_t k_begin = strtoull(argv[2], nullptr, 0), k_end = strtoull(argv[3], nullptr, 0);
+    int dev = 0;
+    std::vector<std::vector<uint8_t>> nonces;
+    std::vector<const char *> names;
+    for (int i = 4; i < argc; ++i) {
+        if (!strcmp(argv[i], "--device") && i + 1 < argc) {
+            dev = atoi(argv[++i]);
+        } else {
+            nonces.push_back(from_hex(argv[i]));
+            names.push_back(argv[i]);
+        }
+    }
+    if (nonces.empty()) return 2;
+    dpow_ctx *ctx = nullptr;
+    int rc = dpow_open(dev, &ctx);
+    if (rc) return fail("dpow_open", rc);
+    std::vector<dpow_census_task> tasks(nonces.size());
+    for (size_t i = 0; i < tasks.size(); ++i) {
+        memset(&tasks[i], 0, sizeof tasks[i]);
+        tasks[i].nonce = nonces[i].data();
+        tasks[i].nonce_len = nonces[i].size();
+        tasks[i].k_begin = k_begin;
+        tasks[i].k_end = k_end;
+    }
+    rc = dpow_census_batch(ctx, tasks.data(), tasks.size(), nullptr);
+    if (rc < 0) return fail("dpow_census_batch", rc);
+    bool all = true;
+    for (size_t i = 0; i < tasks.size(); ++i) {
+        printf("# %s\n", names[i]);
+        print_census(tasks[i].census);
+        all = all && tasks[i].status == DPOW_EXHAUSTED;
+    }
+    dpow_close(ctx);
+    return all ? 0 : 1;
 }
 
 static int cmd_digest(int argc, char **argv) {
@@ -364,6 +410,7 @@ int main(int argc, char **argv) {
     if (argc >= 2 && !strcmp(argv[1], "digest")) return cmd_digest(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "digest-host")) return cmd_digest_host(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "census")) return cmd_census(argc, argv);
+    if (argc >= 2 && !strcmp(argv[1], "census-many")) return cmd_census_many(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "scan")) return cmd_scan(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "batch")) return cmd_batch(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "mine")) return cmd_mine(argc, argv);
@@ -378,6 +425,7 @@ int main(int argc, char **argv) {
             "       dpow_cli batch <ntz> <nonce-hex> [<nonce-hex> ...] [--device N]\n"
             "       dpow_cli scan <nonce-hex> <ntz> <k_begin> <k_end> [worker_byte worker_bits [device]]\n"
             "       dpow_cli census <nonce-hex> <k_begin> <k_end> [worker_byte worker_bits [device]]\n"
+            "       dpow_cli census-many <k_begin> <k_end> <nonce-hex> [<nonce-hex> ...] [--device N]\n"
             "       dpow_cli digest <nonce-hex> <idx> [idx ...] [--device N]\n"
             "       dpow_cli digest-host <nonce-hex> <log2-n> [reps]\n");
     return 2;

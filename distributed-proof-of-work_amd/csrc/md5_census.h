@@ -1,6 +1,7 @@
 // md5_census.h -- the census (dpow_census_window): depth counts and per-depth first hits of a
 // window in one pass.  Definitions shared by the gfx950 kernel (md5_census.hip) and its host loop
-// (census.cpp).
+// (census.cpp), and the depth sink's device code, which the batched census's kernel
+// (md5_census_many.hip) runs as well.
 //
 // A search answers "the first hit at depth N", a scan "which candidates reach depth N"; a census
 // answers "how deep does this window go": for every depth d how many candidates end in at least d
@@ -38,6 +39,103 @@ struct CensusLaunch {
 };
 
 #if defined(__HIPCC__)
+// The depth sink, one source for census_kernel (md5_census.hip) and census_many_kernel
+// (md5_census_many.hip); the comment at the top of md5_census.hip describes it.
+
+constexpr uint32_t kNoOff = 0xFFFFFFFFu;  // "no candidate yet" of a first-index offset (offsets are < kBatchMaxGroup)
+
+// One workgroup's range [lo, hi) of the task, with p / 4 a compile-time constant (md5_batch.h
+// batch_with_w0): 256 candidates per step, one per lane, in increasing index order.  First indices
+// are kept as offsets from `lo` (32 bits) until the workgroup's flush.
+struct CensusGroup {
+    const BatchTask *t;
+    uint32_t *s_cnt, *s_first;  // the workgroup's table (LDS), depths kCensusRare..32 from the lanes
+    uint64_t lo, hi;
+
+    template <int W0>
+    __device__ __forceinline__ void operator()() const {
+        const uint32_t p = t->p, rbits = t->rbits, base_tb = t->base_tb, len_bits = t->len_bits;
+        // the template and the midstate (wave-uniform: SGPRs)
+        uint32_t T[16], iv[4];
+#pragma unroll
+        for (int w = 0; w < 16; ++w) T[w] = t->T[w];
+#pragma unroll
+        for (int w = 0; w < 4; ++w) iv[w] = t->iv[w];
+        // the wave's accumulators of depths 1..kCensusRare - 1 (wave-uniform: SGPRs)
+        uint32_t cnt[kCensusRare - 1], first[kCensusRare - 1];
+#pragma unroll
+        for (uint32_t l = 0; l + 1 < kCensusRare; ++l) cnt[l] = 0u, first[l] = kNoOff;
+        const uint32_t rare_mask = tail_nibble_mask(kCensusRare);  // (folded: a constant)
+        const uint32_t lane = threadIdx.x & 63u;
+        for (uint64_t i0 = lo + (threadIdx.x & ~63u); i0 < hi; i0 += kBlockThreads) {  // i0: the wave's first index
+            uint64_t i = i0 + lane;
+            const bool act = i < hi;
+            if (!act) i = hi - 1;
+            uint32_t M[32];
+            const uint32_t nblk = batch_candidate_words_at<W0>(T, p, rbits, base_tb, len_bits, i, M);
+            uint32_t st[4] = {iv[0], iv[1], iv[2], iv[3]};
+            batch_md5_block(st, M);
+            if constexpr (W0 > 11) {  // p + 1 + L > 55 needs p >= 48
+                if (__any(nblk == 2u)) {
+                    uint32_t s2[4] = {st[0], st[1], st[2], st[3]};
+                    batch_md5_block(s2, M + 16);
+#pragma unroll
+                    for (int w = 0; w < 4; ++w) st[w] = nblk == 2u ? s2[w] : st[w];
+                }
+            }
+            // (the ballot builtin on the compare itself: one v_cmp per mask, the active lanes' mask ANDed in)
+            const unsigned long long active = __builtin_amdgcn_ballot_w64(act);
+#pragma unroll
+            for (uint32_t l = 0; l + 1 < kCensusRare; ++l) {
+                const unsigned long long m =
+                    __builtin_amdgcn_ballot_w64((st[3] & tail_nibble_mask(l + 1u)) == 0u) & active;
+                cnt[l] += (uint32_t)__popcll(m);
+                if (first[l] == kNoOff) {  // (wave-uniform) set once
+                    if (m != 0ull)
+                        first[l] = __builtin_amdgcn_readfirstlane((uint32_t)(i0 - lo)) + (uint32_t)__builtin_ctzll(m);
+                }
+            }
+            const bool rare = act && (st[3] & rare_mask) == 0u;
+            if ((__builtin_amdgcn_ballot_w64((st[3] & rare_mask) == 0u) & active) != 0ull) {
+                if (rare) {
+                    const uint32_t depth = trailing_zero_nibbles(st[0], st[1], st[2], st[3]);
+                    const uint32_t off = (uint32_t)(i - lo);
+                    for (uint32_t d = kCensusRare; d <= depth; ++d) {  // depth <= 32 < kCensusDepths
+                        __hip_atomic_fetch_add(s_cnt + d, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        __hip_atomic_fetch_min(s_first + d, off, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    }
+                }
+            }
+        }
+        // The wave's accumulators join the workgroup's table.
+        if (lane == 0u) {
+#pragma unroll
+            for (uint32_t l = 0; l + 1 < kCensusRare; ++l) {
+                if (cnt[l] != 0u) {
+                    __hip_atomic_fetch_add(s_cnt + l + 1u, cnt[l], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    __hip_atomic_fetch_min(s_first + l + 1u, first[l], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
+            }
+        }
+    }
+};
+
+// The workgroup's flush, after the barrier that completes its table: lane d of the first wave, for
+// each depth with a non-zero count, issues one agent-scope add on cnt[d] and one agent-scope
+// atomicMin on first[d] of `table` (cnt[kCensusDepths] then first[kCensusDepths]), the min skipped
+// when a relaxed load already shows a lower index.
+__device__ __forceinline__ void census_flush(bool work, uint64_t lo, const uint32_t *s_cnt, const uint32_t *s_first,
+                                             uint32_t rbits, uint32_t base_tb, unsigned long long *table) {
+    const uint32_t d = threadIdx.x;
+    if (work && d >= 1u && d < kCensusDepths && s_cnt[d] != 0u) {
+        unsigned long long *const cnt = table, *const first = table + kCensusDepths;
+        const unsigned long long g = global_of_local(lo + s_first[d], rbits, base_tb);
+        __hip_atomic_fetch_add(cnt + d, (unsigned long long)s_cnt[d], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (__hip_atomic_load(first + d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > g)
+            __hip_atomic_fetch_min(first + d, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
 hipError_t census_prepare();
 hipError_t census_launch(const CensusLaunch &C, hipStream_t stream);
 #endif

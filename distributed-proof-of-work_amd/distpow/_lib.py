@@ -114,6 +114,17 @@ class CensusC(ctypes.Structure):
                 ("first_tz", ctypes.c_uint32 * CENSUS_DEPTHS), ("deepest", ctypes.c_uint32)]
 
 
+class CensusTaskC(ctypes.Structure):
+    """dpow_census_task (include/dpow.h)."""
+    _fields_ = [("nonce", ctypes.c_void_p), ("nonce_len", ctypes.c_size_t),
+                ("worker_byte", ctypes.c_uint32), ("worker_bits", ctypes.c_uint32),
+                ("k_begin", ctypes.c_uint64), ("k_end", ctypes.c_uint64), ("k_done", ctypes.c_uint64),
+                ("status", ctypes.c_int32), ("census", CensusC)]
+
+
+CENSUS_MANY_MAX_BLOCKS = 20480  # descriptors of one launch (csrc/md5_census_many.h kCensusManyMaxBlocks)
+
+
 class QueueResultC(ctypes.Structure):
     """dpow_queue_result (include/dpow.h)."""
     _fields_ = [("ticket", ctypes.c_uint64), ("user", ctypes.c_uint64), ("status", ctypes.c_int32),
@@ -295,6 +306,10 @@ def lib():
                                               ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(CensusC), u64p,
                                               ctypes.POINTER(BatchStats)]),
         "dpow_census_merge": (ctypes.c_int, [ctypes.POINTER(CensusC), ctypes.POINTER(CensusC)]),
+        "dpow_census_batch": (ctypes.c_int, [vp, ctypes.POINTER(CensusTaskC), ctypes.c_size_t,
+                                             ctypes.POINTER(BatchStats)]),
+        "dpow_census_plan": (ctypes.c_int, [u64p, u64p, u32p, ctypes.c_size_t, ctypes.c_uint64,
+                                            ctypes.POINTER(BatchRange), ctypes.c_size_t, u64p]),
         "dpow_digests": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_size_t, vp, ctypes.c_size_t, vp, vp, szp,
                                         ctypes.POINTER(BatchStats)]),
         "dpow_digests_device": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_size_t, vp, ctypes.c_size_t, vp, vp,

@@ -18,7 +18,7 @@ from ._lib import (CANCELLED, DPOW_K_LIMIT, DPOW_MAX_SECRET, DPOW_NO_HIT, EXHAUS
 
 __all__ = ["Miner", "SearchResult", "BatchTask", "batch_candidate", "batch_plan", "batch_plan_block",
            "TaskQueue", "QueueResult", "queue_plan", "ScanHit", "scan_slice", "Census",
-           "digest_of_index", "secret_from_index", "md5", "verify", "trailing_zero_nibbles",
+           "CensusTask", "census_plan", "digest_of_index", "secret_from_index", "md5", "verify", "trailing_zero_nibbles",
            "thread_bytes", "remainder_bits", "global_index", "plan_window", "plan_candidate",
            "device_count", "DPOW_NO_HIT", "FOUND", "EXHAUSTED", "CANCELLED"]
 
@@ -230,6 +230,37 @@ class Census:
         into, nxt = self._to_c(), other._to_c()
         check(lib().dpow_census_merge(ctypes.byref(into), ctypes.byref(nxt)), "dpow_census_merge")
         return Census._from_c(into)
+
+
+_CENSUS_TASK_IN = struct.Struct("@PNIIQQ")  # dpow_census_task: the input fields
+_CENSUS_TASK = struct.Struct(f"@PNIIQQQi{_lib.CENSUS_DEPTHS}Q{_lib.CENSUS_DEPTHS}Q{_lib.CENSUS_DEPTHS}II")
+assert _CENSUS_TASK.size == ctypes.sizeof(_lib.CensusTaskC) and _CENSUS_TASK_IN.size == _lib.CensusTaskC.k_done.offset
+
+
+@dataclass
+class CensusTask:
+    """One task of Miner.census_many: the arguments of Miner.census (dpow_census_task)."""
+    nonce: Sequence[int]
+    worker_byte: int = 0
+    worker_bits: int = 0
+    k_begin: int = 0
+    k_end: int = 1
+
+
+def census_plan(windows, cap: int = 0):
+    """The launches dpow_census_batch makes for windows [(k_begin, k_end, worker_bits), ...]
+    (dpow_census_plan): (blocks, launches), blocks a ctypes array of BatchRange, one per workgroup
+    descriptor in launch order, ranges in absolute local indices.  `cap` is a launch's budget of
+    local indices (0: the call's own 2^28)."""
+    n = len(windows)
+    kb = (ctypes.c_uint64 * max(n, 1))(*[w[0] for w in windows])
+    ke = (ctypes.c_uint64 * max(n, 1))(*[w[1] for w in windows])
+    wb = (ctypes.c_uint32 * max(n, 1))(*[w[2] for w in windows])
+    launches = ctypes.c_uint64()
+    cnt = check(lib().dpow_census_plan(kb, ke, wb, n, cap, None, 0, ctypes.byref(launches)), "dpow_census_plan")
+    arr = (_lib.BatchRange * max(cnt, 1))()
+    check(lib().dpow_census_plan(kb, ke, wb, n, cap, arr, cnt, ctypes.byref(launches)), "dpow_census_plan")
+    return (_lib.BatchRange * cnt).from_buffer(arr), launches.value
 
 
 @dataclass
@@ -501,6 +532,37 @@ class Miner:
         (dpow_census_window).  A raised cancel flag ends it early with the census of the part done
         (see `cancelled`; census_page tells how far it got)."""
         return self.census_page(nonce, worker_byte, worker_bits, k_begin, k_end)[1]
+
+    def census_batch(self, tasks: Sequence[CensusTask]):
+        """The census of many windows in one pass over the GPU (dpow_census_batch): one
+        (status, census, k_done) per task, what census_page returns for it.  A raised cancel flag
+        leaves the tasks not finished CANCELLED, each with the complete census of
+        [k_begin, k_done).  The call's launch counts are kept in last_census_many_stats."""
+        n = len(tasks)
+        arr = (_lib.CensusTaskC * max(n, 1))()
+        nonces = [_b(t.nonce) for t in tasks]
+        buf = ctypes.create_string_buffer(b"".join(nonces), max(sum(map(len, nonces)), 1))  # alive for the call
+        addr = ctypes.addressof(buf)
+        raw = (ctypes.c_ubyte * ctypes.sizeof(arr)).from_buffer(arr)
+        for j, (t, nb) in enumerate(zip(tasks, nonces)):  # (packed: a field at a time costs 4096 tasks milliseconds)
+            _CENSUS_TASK_IN.pack_into(raw, j * _CENSUS_TASK.size, addr, len(nb), t.worker_byte, t.worker_bits,
+                                      t.k_begin, t.k_end)
+            addr += len(nb)
+        st = _lib.BatchStats()
+        check(lib().dpow_census_batch(self._ctx, arr, n, ctypes.byref(st)), "dpow_census_batch")
+        self.last_census_many_stats = st
+        D, out = _lib.CENSUS_DEPTHS, []
+        for f in _CENSUS_TASK.iter_unpack(ctypes.string_at(arr, n * _CENSUS_TASK.size)):
+            # (a census the library returns is self-consistent: its set firsts are depths 0..deepest)
+            n_set = f[8 + 3 * D] + 1 if f[8] else 0
+            out.append((f[7], Census(f[8:8 + D], f[8 + D:8 + D + n_set] + (None,) * (D - n_set),
+                                     f[8 + 2 * D:8 + 3 * D], f[8 + 3 * D]), f[6]))
+        return out
+
+    def census_many(self, tasks: Sequence[CensusTask]) -> List[Census]:
+        """`census` for many windows at once (dpow_census_batch): result i is what `census` returns
+        for tasks[i]."""
+        return [c for _, c, _ in self.census_batch(tasks)]
 
     # -- digests ----------------------------------------------------------------
     @staticmethod

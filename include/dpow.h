@@ -37,7 +37,7 @@ extern "C" {
  * The task queue (dpow_queue_*, DPOW_EAGAIN) and dpow_worker_set_queue were added the same way,
  * and so were the scan (dpow_scan, dpow_scan_slice, DPOW_MORE) and the census
  * (dpow_census_window, dpow_census_merge) and the digests (dpow_digests, dpow_digests_device,
- * dpow_digest_of_index).
+ * dpow_digest_of_index) and the batched census (dpow_census_batch, dpow_census_plan).
  * A consumer built against another version must refuse the library before any
  * other call (distpow/_lib.py check_abi, tests/c/abi_harness.c). */
 #define DPOW_ABI_VERSION 5
@@ -258,6 +258,53 @@ int dpow_census_window(dpow_ctx *ctx, const uint8_t *nonce, size_t nonce_len,
                        dpow_census *out, uint64_t *k_done,
                        dpow_batch_stats *stats /* may be NULL */);
 int dpow_census_merge(dpow_census *into, const dpow_census *next);
+
+/* ---------------------------------------------------------------------------
+ * Batched census (added within ABI 5): the census of many tasks in one pass.
+ *
+ * A census of a small window is a launch and a host round trip, not hashing, as a small search is
+ * (dpow_search_batch above): a caller that wants the depth profile of B nonces -- a cache
+ * refreshing its dominant secrets, a difficulty calibration over fresh nonces, an audit of what a
+ * batch returned -- pays them once per launch here instead of once per task.  Each task is a
+ * dpow_census_window argument tuple, and tasks[i].census is exactly what dpow_census_window writes
+ * for it on an idle context, first_tz included.  Tasks are independent; duplicates are legal and
+ * each gets its own full answer.
+ *
+ * One generic kernel (csrc/md5_census_many.hip) hashes the tasks in array order, one bounded launch
+ * per 2^28 local indices of the tasks taken together: a launch holds as many whole tasks as fit and
+ * at most one task cut at its end, which goes on in the next launch (DESIGN.md section 16;
+ * dpow_census_plan below).  After each launch the host checks every task's table, recomputes
+ * every first index with the host MD5 (a failure is DPOW_EVERIFY) and folds it as
+ * dpow_census_window does.
+ *
+ * Returns 0, or a negative code with no task written: DPOW_EINVAL for a NULL ctx or tasks, n_tasks
+ * of 0 or above DPOW_BATCH_MAX, worker_byte > 255, k_begin > k_end, a NULL nonce with a non-zero
+ * nonce_len, a nonce longer than DPOW_MAX_NONCE or a context with a node slot attached; DPOW_ERANGE
+ * for k_end > DPOW_K_LIMIT; all of these before any GPU work (stats may be NULL).  On 0 every task
+ * has its status: DPOW_EXHAUSTED, k_done = k_end and the census of its window; a task with
+ * k_begin == k_end is DPOW_EXHAUSTED with the empty census and takes no GPU work, and a call whose
+ * tasks are all empty makes no launch.  The context's cancel flag is checked on entry and between
+ * launches.  Raised on entry: every task is DPOW_CANCELLED with k_done = k_begin and the empty
+ * census, without a launch.  Raised between launches: the tasks finished by then are
+ * DPOW_EXHAUSTED; the task a launch boundary cut is DPOW_CANCELLED with k_done at the cut and the
+ * complete census of [k_begin, k_done), so the caller continues from k_done and merges
+ * (dpow_census_merge); the tasks not begun are DPOW_CANCELLED with k_done = k_begin and the empty
+ * census (an empty task among them is DPOW_EXHAUSTED all the same).  One search, batch, scan,
+ * census or digest call is in flight per context.  dpow_search_bound has no effect on the call,
+ * and it does not touch dpow_stats: stats->launches = stats->rounds = its launches,
+ * stats->candidates = the local indices they covered, stats->kernel_ms = their durations.
+ * ------------------------------------------------------------------------- */
+typedef struct dpow_census_task {
+    const uint8_t *nonce; size_t nonce_len;      /* in */
+    uint32_t worker_byte, worker_bits;           /* in */
+    uint64_t k_begin, k_end;                     /* in */
+    uint64_t k_done;                             /* out */
+    int32_t status;                              /* out: DPOW_EXHAUSTED / DPOW_CANCELLED */
+    dpow_census census;                          /* out: the complete census of [k_begin, k_done) */
+} dpow_census_task;
+int dpow_census_batch(dpow_ctx *ctx, dpow_census_task *tasks, size_t n_tasks,
+                      dpow_batch_stats *stats /* may be NULL */);
+/* (dpow_census_plan, the call's launch planner, is with the host helpers below.) */
 
 /* ---------------------------------------------------------------------------
  * Digests (added within ABI 5): MD5 and depth of any listed candidates in one pass.
@@ -603,6 +650,24 @@ int dpow_batch_plan_block(const dpow_batch_range *entries, uint32_t n_live, uint
  * DPOW_BATCH_MAX, a left[i] of 0); *budget_out = the launch's candidate budget. */
 int dpow_queue_plan(const uint64_t *left, const uint32_t *age, size_t n_tasks,
                     dpow_batch_range *out, size_t max_blocks, uint64_t *budget_out);
+
+/* The batched census's launch planner (host logic of dpow_census_batch, exposed for testing;
+ * DESIGN.md section 16) for tasks with windows [k_begin[i], k_end[i]) and partitions
+ * worker_bits[i].  A launch takes tasks in array order until it holds `cap` local indices (0: the
+ * call's own 2^28; else 256..2^28, rounded down to a multiple of 256); only its last task can be
+ * cut, at a multiple of 256 local indices from the task's begin, and goes on in the next launch.
+ * One entry per workgroup descriptor, in launch order and within a launch in task order: launch =
+ * the launch number, task = the task index, [i_begin, i_end) the descriptor's absolute local index
+ * range (k * R + t), group = the launch's block size -- the descriptors of a task's part are that
+ * long, the last one possibly shorter, none above 16384 -- and rows = the task's descriptor count
+ * in that launch.  An empty task has no entry; no launch has more than 20480.  Returns the number
+ * of entries (may exceed max_entries, in which case only the first max_entries are written) or a
+ * negative code (DPOW_EINVAL: a NULL argument, n_tasks of 0 or above DPOW_BATCH_MAX, k_begin >
+ * k_end, a cap outside its range; DPOW_ERANGE: k_end > DPOW_K_LIMIT, more than INT32_MAX entries);
+ * *launches_out = launches. */
+int dpow_census_plan(const uint64_t *k_begin, const uint64_t *k_end, const uint32_t *worker_bits,
+                     size_t n_tasks, uint64_t cap, dpow_batch_range *out, size_t max_entries,
+                     uint64_t *launches_out);
 
 /* The scan's slice rule (host logic of dpow_scan, exposed for testing):
  * the local indices one launch of a scan for `ntz` covers when its hit list holds `capacity`

@@ -34,6 +34,9 @@
 #   census [reps] [n=lib.so ...]   the census's GPU tests, then its rate beside scan_kernel's, the dense window and
 #                    a fixture window beside the scan (tools/census_rate.py -> census_rate.json); n=lib.so:
 #                    libraries built with EXTRA=-DDPOW_CENSUS_RARE=n, for the kCensusRare comparison
+#   census-many [reps]   the batched census's GPU tests, then its kernel's rate beside census_kernel's, its
+#                    tasks per second beside the looped census and where a call's time goes
+#                    (tools/census_many_rate.py -> census_many_rate.json)
 #   digest [reps] [chunk-lib.so]   the digests' GPU tests, then the kernel's rate beside scan_kernel's, the host
 #                    call beside the host loops, the two stagings and the chunk sizes (tools/digest_rate.py ->
 #                    digest_rate.json); chunk-lib.so: a library built with EXTRA=-DDPOW_DIGEST_CHUNK_LOG2=20
@@ -132,6 +135,10 @@ census)
     timeout -k 10 300 python3 -u -m pytest tests/test_gpu_census.py -m gpu -x -v -s > $out/pytest_census.txt 2>&1 &&
     timeout -k 10 300 python3 -u tools/census_rate.py --reps "$reps" --out $out/census_rate.json "${rare[@]}" \
         > $out/census_rate.txt 2> $out/census_rate.err ;;
+census-many)
+    timeout -k 10 300 python3 -u -m pytest tests/test_gpu_census_many.py -m gpu -x -v -s > $out/pytest_census_many.txt 2>&1 &&
+    timeout -k 10 400 python3 -u tools/census_many_rate.py --reps "${1:-5}" --out $out/census_many_rate.json \
+        > $out/census_many_rate.txt 2> $out/census_many_rate.err ;;
 digest)
     reps=${1:-5}; lib=()
     [ -n "$2" ] && lib=(--chunk-lib "$2")
