@@ -136,6 +136,7 @@ struct BatchState;  // batch.h
 struct ScanState;   // scan.h
 struct CensusState;  // census.h
 struct CensusManyState;  // census_many.h
+struct ScanManyState;  // scan_many.h
 struct DigestState;  // digests.h
 
 // The body of dpow_search (arguments checked): search.cpp.
@@ -204,6 +205,7 @@ struct __attribute__((visibility("default"))) dpow_ctx {
     dpow::ScanState *scan = nullptr;    // buffers of dpow_scan: allocated by the first scan (scan.cpp)
     dpow::CensusState *census = nullptr;  // buffers of dpow_census_window: allocated by the first census (census.cpp)
     dpow::CensusManyState *census_many = nullptr;  // buffers of dpow_census_batch: allocated by the first call (census_many.cpp)
+    dpow::ScanManyState *scan_many = nullptr;  // buffers of dpow_scan_batch: allocated by the first call (scan_many.cpp)
     dpow::DigestState *digests = nullptr;  // buffers of dpow_digests: allocated by the first call (digests.cpp)
 };
 

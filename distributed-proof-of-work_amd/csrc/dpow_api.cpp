@@ -1,7 +1,7 @@
 // dpow_api.cpp -- the C ABI (include/dpow.h) over the gfx950 search kernels: the context's
 // lifecycle (dpow_open, dpow_close), its accessors and stats, the argument-checking entry points
 // of the searches (dpow_search: search.cpp; dpow_search_batch: batch.cpp; dpow_scan: scan.cpp;
-// dpow_census_window: census.cpp; dpow_census_batch: census_many.cpp; dpow_digests, dpow_digests_device: digests.cpp; dpow_search_bound) and the pure host helpers.  The node layer is node.cpp, the dpow_diag_* entry points diag.cpp.
+// dpow_census_window: census.cpp; dpow_census_batch: census_many.cpp; dpow_scan_batch: scan_many.cpp; dpow_digests, dpow_digests_device: digests.cpp; dpow_search_bound) and the pure host helpers.  The node layer is node.cpp, the dpow_diag_* entry points diag.cpp.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -19,6 +19,7 @@
 #include "md5_host.h"
 #include "md5_variants.h"
 #include "scan.h"
+#include "scan_many.h"
 
 using namespace dpow;
 
@@ -185,6 +186,7 @@ void dpow_close(dpow_ctx *c) {
     scan_free(c->scan);
     census_free(c->census);
     census_many_free(c->census_many);
+    scan_many_free(c->scan_many);
     digests_free(c->digests);
     if (c->d_ctrl_alloc) (void)hipFree(c->d_ctrl_alloc);
     if (c->d_claims) (void)hipFree(c->d_claims);
@@ -313,6 +315,18 @@ int dpow_scan(dpow_ctx *c, const uint8_t *nonce, size_t nonce_len, uint32_t ntz,
     c->last_use.store(now_ns(), std::memory_order_relaxed);
     return scan_run(&c->scan, c->stream, c->h_cancel, nonce, nonce_len, ntz, worker_byte, worker_bits, k_begin, k_end,
                     out, max_hits, n_hits, k_done, stats);
+}
+
+int dpow_scan_batch(dpow_ctx *c, dpow_scan_task *tasks, size_t n_tasks, dpow_scan_hit *out, size_t max_hits,
+                    size_t *n_out, dpow_batch_stats *stats) {
+    const int rc = scan_many_check(tasks, n_tasks, out, max_hits, n_out);  // the call's own errors first: they need no context
+    if (rc < 0) return rc;
+    if (!c) return set_error(DPOW_EINVAL, "dpow_scan_batch: ctx is NULL");
+    if (c->node) return set_error(DPOW_EINVAL, "dpow_scan_batch: a node slot is attached to the context");
+    const DeviceScope on_device(c->device);
+    if (on_device.e != hipSuccess) return hip_fail(on_device.e, "hipSetDevice");
+    c->last_use.store(now_ns(), std::memory_order_relaxed);
+    return scan_many_run(&c->scan_many, c->stream, c->h_cancel, tasks, n_tasks, out, max_hits, n_out, stats);
 }
 
 int dpow_census_window(dpow_ctx *c, const uint8_t *nonce, size_t nonce_len, uint32_t worker_byte,

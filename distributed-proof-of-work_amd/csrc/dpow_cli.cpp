@@ -19,6 +19,9 @@
 //       how deep the window goes (dpow_census_window), one line per depth up to the deepest: the
 //       depth, the number of candidates at least that deep, the first one's global index and its
 //       secret in hex
+//   dpow_cli scan-many <ntz> <k_begin> <k_end> <nonce-hex> [<nonce-hex> ...] [--device N]
+//       every hit of the same window of every nonce in batched calls (dpow_scan_batch), one line
+//       per hit: the nonce's number (from 0), then `scan`'s line
 //   dpow_cli census-many <k_begin> <k_end> <nonce-hex> [<nonce-hex> ...] [--device N]
 //       the census of the same window of every nonce in one batched call (dpow_census_batch): per
 //       task a line "# <nonce-hex>" and then `census`'s lines
@@ -348,6 +351,57 @@ static int cmd_census_many(int argc, char **argv) {
     return all ? 0 : 1;
 }
 
+// One line per hit: the task's number, then dpow_cli scan's line.  The unfinished tasks go in again
+// from their k_done until every one is exhausted.
+static int cmd_scan_many(int argc, char **argv) {
+    if (argc < 6) return 2;
+    const uint32_t ntz = (uint32_t)atoi(argv[2]);
+    const uint64_t k_begin = strtoull(argv[3], nullptr, 0), k_end = strtoull(argv[4], nullptr, 0);
+    int dev = 0;
+    std::vector<std::vector<uint8_t>> nonces;
+    for (int i = 5; i < argc; ++i) {
+        if (!strcmp(argv[i], "--device") && i + 1 < argc) dev = atoi(argv[++i]);
+        else nonces.push_back(from_hex(argv[i]));
+    }
+    if (nonces.empty()) return 2;
+    dpow_ctx *ctx = nullptr;
+    int rc = dpow_open(dev, &ctx);
+    if (rc) return fail("dpow_open", rc);
+    std::vector<uint64_t> k(nonces.size(), k_begin);
+    std::vector<size_t> todo(nonces.size());
+    for (size_t i = 0; i < todo.size(); ++i) todo[i] = i;
+    std::vector<dpow_scan_hit> page(1u << 16);
+    bool cancelled = false;
+    while (!todo.empty() && !cancelled) {
+        std::vector<dpow_scan_task> tasks(todo.size());
+        for (size_t j = 0; j < tasks.size(); ++j) {
+            memset(&tasks[j], 0, sizeof tasks[j]);
+            tasks[j].nonce = nonces[todo[j]].data();
+            tasks[j].nonce_len = nonces[todo[j]].size();
+            tasks[j].ntz = ntz;
+            tasks[j].k_begin = k[todo[j]];
+            tasks[j].k_end = k_end;
+        }
+        size_t n = 0;
+        rc = dpow_scan_batch(ctx, tasks.data(), tasks.size(), page.data(), page.size(), &n, nullptr);
+        if (rc < 0) return fail("dpow_scan_batch", rc);
+        std::vector<size_t> next;
+        for (size_t j = 0; j < tasks.size(); ++j) {
+            for (uint64_t h = tasks[j].first_hit; h < tasks[j].first_hit + tasks[j].n_hits; ++h) {
+                printf("%zu %llu %u ", todo[j], (unsigned long long)page[h].global_idx, page[h].tz);
+                for (uint32_t b = 0; b < page[h].secret_len; ++b) printf("%02x", page[h].secret[b]);
+                printf("\n");
+            }
+            k[todo[j]] = tasks[j].k_done;
+            if (tasks[j].status == DPOW_MORE) next.push_back(todo[j]);
+            cancelled = cancelled || tasks[j].status == DPOW_CANCELLED;
+        }
+        todo.swap(next);
+    }
+    dpow_close(ctx);
+    return cancelled ? 1 : 0;
+}
+
 static int cmd_digest(int argc, char **argv) {
     if (argc < 4) return 2;
     std::vector<uint8_t> nonce = from_hex(argv[2]);
@@ -412,6 +466,7 @@ int main(int argc, char **argv) {
     if (argc >= 2 && !strcmp(argv[1], "census")) return cmd_census(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "census-many")) return cmd_census_many(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "scan")) return cmd_scan(argc, argv);
+    if (argc >= 2 && !strcmp(argv[1], "scan-many")) return cmd_scan_many(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "batch")) return cmd_batch(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "mine")) return cmd_mine(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "sweep")) return cmd_sweep(argc, argv);
@@ -424,6 +479,7 @@ int main(int argc, char **argv) {
             "       dpow_cli latency [reps [device]]\n"
             "       dpow_cli batch <ntz> <nonce-hex> [<nonce-hex> ...] [--device N]\n"
             "       dpow_cli scan <nonce-hex> <ntz> <k_begin> <k_end> [worker_byte worker_bits [device]]\n"
+            "       dpow_cli scan-many <ntz> <k_begin> <k_end> <nonce-hex> [<nonce-hex> ...] [--device N]\n"
             "       dpow_cli census <nonce-hex> <k_begin> <k_end> [worker_byte worker_bits [device]]\n"
             "       dpow_cli census-many <k_begin> <k_end> <nonce-hex> [<nonce-hex> ...] [--device N]\n"
             "       dpow_cli digest <nonce-hex> <idx> [idx ...] [--device N]\n"

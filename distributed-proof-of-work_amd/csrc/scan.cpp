@@ -44,6 +44,20 @@ uint64_t scan_slice(uint32_t ntz, uint32_t capacity) {
     return std::max<uint64_t>(slice, 256u);
 }
 
+bool scan_fill_hit(uint8_t *msg, size_t nonce_len, uint64_t g, uint32_t ntz, dpow_scan_hit &h) {
+    size_t len = 0;
+    dpow_secret_from_index(g, h.secret, &len);
+    memset(h.secret + len, 0, DPOW_MAX_SECRET - len);
+    memcpy(msg + nonce_len, h.secret, len);
+    uint8_t d[16];
+    md5_digest(msg, nonce_len + len, d);
+    h.tz = digest_trailing_zero_nibbles(d);
+    if (h.tz < ntz) return false;
+    h.global_idx = g;
+    h.secret_len = (uint32_t)len;
+    return true;
+}
+
 // The context's buffers.  Device: the hit list in the engine's image area, the control words behind
 // it (batch_engine.h) with the launch's hit count at +16.  Pinned: the list's copy, the count, the
 // record.
@@ -163,17 +177,8 @@ int scan_run(ScanState **state, hipStream_t stream, const volatile uint32_t *can
                 if (n_out + n_k > max_hits) return finish(DPOW_MORE, g >> 8);
                 prev_k = g >> 8;
             }
-            dpow_scan_hit &h = out[n_out];
-            size_t len = 0;
-            dpow_secret_from_index(g, h.secret, &len);
-            memset(h.secret + len, 0, DPOW_MAX_SECRET - len);
-            memcpy(msg.data() + nonce_len, h.secret, len);
-            uint8_t d[16];
-            md5_digest(msg.data(), nonce_len + len, d);
-            h.tz = digest_trailing_zero_nibbles(d);
-            if (h.tz < ntz) return set_error(DPOW_EVERIFY, "dpow_scan: kernel hit failed host MD5 verification");
-            h.global_idx = g;
-            h.secret_len = (uint32_t)len;
+            if (!scan_fill_hit(msg.data(), nonce_len, g, ntz, out[n_out]))
+                return set_error(DPOW_EVERIFY, "dpow_scan: kernel hit failed host MD5 verification");
             ++n_out;
         }
         i_cur = hi;

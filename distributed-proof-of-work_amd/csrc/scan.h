@@ -14,6 +14,11 @@ namespace dpow {
 // are at most capacity / 4 wherever the slice is above 256.
 uint64_t scan_slice(uint32_t ntz, uint32_t capacity);
 
+// One verified entry, the step dpow_scan and dpow_scan_batch share: `h` for global index g from the
+// host MD5 of nonce || secret (msg: the nonce followed by DPOW_MAX_SECRET bytes of room).  False,
+// with h.tz the depth found, when that is below ntz.
+bool scan_fill_hit(uint8_t *msg, size_t nonce_len, uint64_t g, uint32_t ntz, dpow_scan_hit &h);
+
 // Device and pinned buffers of a context's scans: allocated on its first scan, freed with it.
 struct ScanState;
 void scan_free(ScanState *s);  // the context's device is current, its stream drained

@@ -125,6 +125,17 @@ class CensusTaskC(ctypes.Structure):
 CENSUS_MANY_MAX_BLOCKS = 20480  # descriptors of one launch (csrc/md5_census_many.h kCensusManyMaxBlocks)
 
 
+class ScanTaskC(ctypes.Structure):
+    """dpow_scan_task (include/dpow.h)."""
+    _fields_ = [("nonce", ctypes.c_void_p), ("nonce_len", ctypes.c_size_t), ("ntz", ctypes.c_uint32),
+                ("worker_byte", ctypes.c_uint32), ("worker_bits", ctypes.c_uint32),
+                ("k_begin", ctypes.c_uint64), ("k_end", ctypes.c_uint64), ("k_done", ctypes.c_uint64),
+                ("status", ctypes.c_int32), ("first_hit", ctypes.c_uint64), ("n_hits", ctypes.c_uint64)]
+
+
+SCAN_MANY_MAX_BLOCKS = 20480  # descriptors of one launch (csrc/md5_scan_many.h kScanManyMaxBlocks)
+
+
 class QueueResultC(ctypes.Structure):
     """dpow_queue_result (include/dpow.h)."""
     _fields_ = [("ticket", ctypes.c_uint64), ("user", ctypes.c_uint64), ("status", ctypes.c_int32),
@@ -310,6 +321,11 @@ def lib():
                                              ctypes.POINTER(BatchStats)]),
         "dpow_census_plan": (ctypes.c_int, [u64p, u64p, u32p, ctypes.c_size_t, ctypes.c_uint64,
                                             ctypes.POINTER(BatchRange), ctypes.c_size_t, u64p]),
+        "dpow_scan_batch": (ctypes.c_int, [vp, ctypes.POINTER(ScanTaskC), ctypes.c_size_t, ctypes.POINTER(ScanHitC),
+                                           ctypes.c_size_t, szp, ctypes.POINTER(BatchStats)]),
+        "dpow_scan_plan": (ctypes.c_int, [u64p, u64p, u32p, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint32,
+                                          ctypes.POINTER(BatchRange), ctypes.c_size_t, u64p]),
+        "dpow_scan_plan_halve": (None, [ctypes.c_uint64, ctypes.c_uint64, u64p, u32p]),
         "dpow_digests": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_size_t, vp, ctypes.c_size_t, vp, vp, szp,
                                         ctypes.POINTER(BatchStats)]),
         "dpow_digests_device": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_size_t, vp, ctypes.c_size_t, vp, vp,

@@ -17,7 +17,7 @@ from ._lib import (CANCELLED, DPOW_K_LIMIT, DPOW_MAX_SECRET, DPOW_NO_HIT, EXHAUS
                    PlanLaunch, Stats, check, lib)
 
 __all__ = ["Miner", "SearchResult", "BatchTask", "batch_candidate", "batch_plan", "batch_plan_block",
-           "TaskQueue", "QueueResult", "queue_plan", "ScanHit", "scan_slice", "Census",
+           "TaskQueue", "QueueResult", "queue_plan", "ScanHit", "scan_slice", "ScanTask", "scan_plan", "scan_plan_halve", "Census",
            "CensusTask", "census_plan", "digest_of_index", "secret_from_index", "md5", "verify", "trailing_zero_nibbles",
            "thread_bytes", "remainder_bits", "global_index", "plan_window", "plan_candidate",
            "device_count", "DPOW_NO_HIT", "FOUND", "EXHAUSTED", "CANCELLED"]
@@ -186,6 +186,47 @@ class ScanHit:
 def scan_slice(num_trailing_zeros: int, capacity: int = _lib.SCAN_CAP) -> int:
     """Local indices per launch of a scan whose hit list holds `capacity` entries (dpow_scan_slice)."""
     return lib().dpow_scan_slice(num_trailing_zeros, capacity)
+
+
+_SCAN_TASK_IN = struct.Struct("@PNIIIQQ")  # dpow_scan_task: the input fields
+_SCAN_TASK = struct.Struct("@PNIIIQQQiQQ")
+assert _SCAN_TASK.size == ctypes.sizeof(_lib.ScanTaskC) and _SCAN_TASK_IN.size == _lib.ScanTaskC.k_done.offset
+
+
+@dataclass
+class ScanTask:
+    """One task of Miner.scan_many: the arguments of Miner.scan (dpow_scan_task)."""
+    nonce: Sequence[int]
+    num_trailing_zeros: int
+    worker_byte: int = 0
+    worker_bits: int = 0
+    k_begin: int = 0
+    k_end: int = 1
+
+
+def scan_plan(windows, cap: int = 0, capacity: int = 0):
+    """The launches dpow_scan_batch makes for windows [(i_begin, i_end, num_trailing_zeros), ...] of
+    local indices (dpow_scan_plan): (blocks, launches), blocks a ctypes array of BatchRange, one per
+    workgroup descriptor in launch order, ranges in absolute local indices.  `cap` is a launch's
+    budget of local indices (0: the call's own 2^28), `capacity` the hit list's, a quarter of which
+    is a launch's budget of hit weight (0: the call's own 65536)."""
+    n = len(windows)
+    ib = (ctypes.c_uint64 * max(n, 1))(*[w[0] for w in windows])
+    ie = (ctypes.c_uint64 * max(n, 1))(*[w[1] for w in windows])
+    nz = (ctypes.c_uint32 * max(n, 1))(*[w[2] for w in windows])
+    launches = ctypes.c_uint64()
+    cnt = check(lib().dpow_scan_plan(ib, ie, nz, n, cap, capacity, None, 0, ctypes.byref(launches)), "dpow_scan_plan")
+    arr = (_lib.BatchRange * max(cnt, 1))()
+    check(lib().dpow_scan_plan(ib, ie, nz, n, cap, capacity, arr, cnt, ctypes.byref(launches)), "dpow_scan_plan")
+    return (_lib.BatchRange * cnt).from_buffer(arr), launches.value
+
+
+def scan_plan_halve(total: int, weight: int):
+    """(cap, capacity) dpow_scan_batch plans a launch's parts with again after the launch, of `total`
+    local indices and hit weight `weight`, overflowed its list (dpow_scan_plan_halve)."""
+    cap, capacity = ctypes.c_uint64(), ctypes.c_uint32()
+    lib().dpow_scan_plan_halve(total, weight, ctypes.byref(cap), ctypes.byref(capacity))
+    return cap.value, capacity.value
 
 
 @dataclass(frozen=True)
@@ -510,6 +551,51 @@ class Miner:
             out += hits
             if r != _lib.MORE:
                 return out
+
+    def scan_batch(self, tasks: Sequence[ScanTask], max_hits: int = _lib.SCAN_CAP):
+        """Every hit of many windows in one pass over the GPU (dpow_scan_batch): one
+        (status, hits, k_done) per task, what scan_page returns for it while `max_hits` hits of the
+        tasks together have room.  The task that does not fit is MORE from its k_done, the tasks
+        behind it MORE from their k_begin; a raised cancel flag leaves the tasks not finished
+        CANCELLED likewise.  The call's launch counts are kept in last_scan_many_stats."""
+        n = len(tasks)
+        arr = (_lib.ScanTaskC * max(n, 1))()
+        nonces = [_b(t.nonce) for t in tasks]
+        buf = ctypes.create_string_buffer(b"".join(nonces), max(sum(map(len, nonces)), 1))  # alive for the call
+        addr = ctypes.addressof(buf)
+        raw = (ctypes.c_ubyte * ctypes.sizeof(arr)).from_buffer(arr)
+        for j, (t, nb) in enumerate(zip(tasks, nonces)):  # (packed: a field at a time costs 4096 tasks milliseconds)
+            _SCAN_TASK_IN.pack_into(raw, j * _SCAN_TASK.size, addr, len(nb), t.num_trailing_zeros, t.worker_byte,
+                                    t.worker_bits, t.k_begin, t.k_end)
+            addr += len(nb)
+        hits_c = (_lib.ScanHitC * max(max_hits, 1))()
+        cnt, st = ctypes.c_size_t(), _lib.BatchStats()
+        check(lib().dpow_scan_batch(self._ctx, arr, n, hits_c, max_hits, ctypes.byref(cnt), ctypes.byref(st)),
+              "dpow_scan_batch")
+        self.last_scan_many_stats = st
+        hits = [ScanHit(g, tz, sec[:slen])
+                for g, tz, slen, sec in _SCAN_HIT.iter_unpack(ctypes.string_at(hits_c, cnt.value * _SCAN_HIT.size))]
+        return [(f[8], hits[f[9]:f[9] + f[10]], f[7])
+                for f in _SCAN_TASK.iter_unpack(ctypes.string_at(arr, n * _SCAN_TASK.size))]
+
+    def scan_many(self, tasks: Sequence[ScanTask], max_hits: int = _lib.SCAN_CAP) -> List[List[ScanHit]]:
+        """`scan` for many windows at once (dpow_scan_batch, the unfinished tasks submitted again
+        over MORE; max_hits is the page size): result i is what `scan` returns for tasks[i].  A
+        raised cancel flag ends it early with the hits found so far (see `cancelled`)."""
+        out: List[List[ScanHit]] = [[] for _ in tasks]
+        todo = list(range(len(tasks)))
+        k = [t.k_begin for t in tasks]
+        while todo:
+            batch = todo[:_lib.DPOW_BATCH_MAX]  # at most DPOW_BATCH_MAX tasks per call
+            res = self.scan_batch([ScanTask(tasks[i].nonce, tasks[i].num_trailing_zeros, tasks[i].worker_byte,
+                                            tasks[i].worker_bits, k[i], tasks[i].k_end) for i in batch], max_hits)
+            for i, (r, hits, k_done) in zip(batch, res):
+                out[i] += hits
+                k[i] = k_done
+            if any(r == CANCELLED for r, _, _ in res):
+                break
+            todo = [i for i, (r, _, _) in zip(batch, res) if r == _lib.MORE] + todo[len(batch):]
+        return out
 
     # -- census -----------------------------------------------------------------
     def census_page(self, nonce: Sequence[int], worker_byte: int = 0, worker_bits: int = 0, k_begin: int = 0,

@@ -37,7 +37,8 @@ extern "C" {
  * The task queue (dpow_queue_*, DPOW_EAGAIN) and dpow_worker_set_queue were added the same way,
  * and so were the scan (dpow_scan, dpow_scan_slice, DPOW_MORE) and the census
  * (dpow_census_window, dpow_census_merge) and the digests (dpow_digests, dpow_digests_device,
- * dpow_digest_of_index) and the batched census (dpow_census_batch, dpow_census_plan).
+ * dpow_digest_of_index) and the batched census (dpow_census_batch, dpow_census_plan) and the
+ * batched scan (dpow_scan_batch, dpow_scan_plan, dpow_scan_plan_halve).
  * A consumer built against another version must refuse the library before any
  * other call (distpow/_lib.py check_abi, tests/c/abi_harness.c). */
 #define DPOW_ABI_VERSION 5
@@ -204,6 +205,58 @@ int dpow_scan(dpow_ctx *ctx, const uint8_t *nonce, size_t nonce_len, uint32_t nt
               dpow_scan_hit *out, size_t max_hits, size_t *n_hits, uint64_t *k_done,
               dpow_batch_stats *stats /* may be NULL */);
 /* (dpow_scan_slice, the scan's slice rule, is with the host helpers below.) */
+
+/* ---------------------------------------------------------------------------
+ * Batched scan (added within ABI 5): every hit of many windows in one pass.
+ *
+ * A scan of a small window is a launch and a host round trip, not hashing, as a small search or
+ * census is (dpow_search_batch, dpow_census_batch): a caller that wants the hit lists of B
+ * windows -- a cache refreshing its dominant secrets, a difficulty calibration over fresh nonces,
+ * an audit of what a batch returned -- pays them once per launch here instead of once per task.
+ * Each task is a dpow_scan argument tuple, and its hits are exactly what dpow_scan writes for it on
+ * an idle context: every candidate of its partition over [k_begin, k_done) with depth >= its ntz,
+ * in increasing global index, tz and secret from the host MD5.  Tasks are independent; duplicates
+ * are legal and each gets its own copy; ntz = 0 makes every candidate a hit and ntz > 32 finds
+ * nothing.
+ *
+ * One generic kernel (csrc/md5_scan_many.hip) hashes the tasks in array order, one bounded launch
+ * per 2^28 local indices or a quarter of its hit list's worth of expected hits, whichever is less,
+ * of the tasks taken together: a launch holds as many whole tasks as fit and at most one task cut
+ * at its end (dpow_scan_plan below).  The hits go to `out`, each task's
+ * contiguous and the tasks' in array order: task i's are out[first_hit .. first_hit + n_hits),
+ * and *n_out is the total.
+ *
+ * Returns 0 with every task's status set, or a negative code with no task and nothing of `out`
+ * written: dpow_census_batch's argument errors, and DPOW_EINVAL for max_hits < 256 or a NULL `out`
+ * or `n_out`; all of these before any GPU work (stats may be NULL); DPOW_EVERIFY for a device
+ * entry that fails the host's checks.  On 0 a finished task is DPOW_EXHAUSTED with k_done = k_end;
+ * a task with k_begin == k_end is DPOW_EXHAUSTED without GPU work whenever the call gets past its
+ * entry check, and a call whose tasks are all empty makes no launch and allocates nothing.
+ * Paging: when `out` cannot take the next whole k of the task being written the call stops; that
+ * task is DPOW_MORE with k_done at that k and the complete hits of [k_begin, k_done), every task
+ * after it is DPOW_MORE with k_done = k_begin and no hits, and the caller submits the unfinished
+ * tasks again from their k_done.  A k's hits are never split, and max_hits >= 256 lets the first
+ * unfinished task make progress in every call.  The context's cancel flag is checked on entry and
+ * between launches.  Raised on entry: every task is DPOW_CANCELLED with k_done = k_begin, without
+ * a launch.  Raised between launches: the tasks finished by then are DPOW_EXHAUSTED, the task a
+ * launch boundary cut is DPOW_CANCELLED at a whole k with its hits so far complete, the tasks not
+ * begun are DPOW_CANCELLED with k_done = k_begin.  One search, batch, scan, census or digest call
+ * is in flight per context.  dpow_search_bound has no effect on the call, and it does not touch
+ * dpow_stats: its counts go to *stats as dpow_census_batch's do (an overflowed launch, which is
+ * discarded and re-planned, counts as well).
+ * ------------------------------------------------------------------------- */
+typedef struct dpow_scan_task {
+    const uint8_t *nonce; size_t nonce_len;        /* in */
+    uint32_t ntz, worker_byte, worker_bits;        /* in */
+    uint64_t k_begin, k_end;                       /* in */
+    uint64_t k_done;                               /* out */
+    int32_t  status;                               /* out: DPOW_EXHAUSTED / DPOW_MORE / DPOW_CANCELLED */
+    uint64_t first_hit, n_hits;                    /* out: out[first_hit .. first_hit + n_hits) */
+} dpow_scan_task;
+int dpow_scan_batch(dpow_ctx *ctx, dpow_scan_task *tasks, size_t n_tasks,
+                    dpow_scan_hit *out, size_t max_hits, size_t *n_out,
+                    dpow_batch_stats *stats /* may be NULL */);
+/* (dpow_scan_plan, the call's launch planner, is with the host helpers below.) */
 
 /* ---------------------------------------------------------------------------
  * Census (added within ABI 5): depth counts and per-depth first hits of a window in one pass.
@@ -675,6 +728,32 @@ int dpow_census_plan(const uint64_t *k_begin, const uint64_t *k_end, const uint3
  * [256, 2^28]; its expected hits, slice / 16^min(ntz, 32), are at most capacity / 4 wherever
  * the slice is above 256. */
 uint64_t dpow_scan_slice(uint32_t ntz, uint32_t capacity);
+
+/* The batched scan's launch planner (host logic of dpow_scan_batch, exposed for testing; DESIGN.md
+ * section 17) for tasks with local index ranges [i_begin[i], i_end[i]) (k * R + t, R = 256 >>
+ * worker_bits % 9 candidates per k) and depths ntz[i].  A launch takes tasks in array order under
+ * two budgets: its local indices total at most `cap` (0: the call's own 2^28; else 256..2^28,
+ * rounded down to a multiple of 256), and its hit weight at most capacity / 4, where `capacity`
+ * is the hit list's (0: the call's own 65536; else 1024..65536, rounded down to a multiple of
+ * 1024) and a part of n indices at depth N weighs ceil(n / 16^min(N, 7)).  Only its last task
+ * can be cut, at a multiple of 256 local indices from the task's begin, and goes on in the next
+ * launch; a launch takes at least 256 indices or what is left of a task.  For one task the launches
+ * are dpow_scan's (dpow_scan_slice).  The entries are dpow_census_plan's: one per workgroup
+ * descriptor, in launch order and within a launch in task order, none above 16384 indices, no
+ * launch with more than 20480, no entry for an empty task.  Returns the number of entries (may
+ * exceed max_entries, in which case only the first max_entries are written) or a negative code
+ * (DPOW_EINVAL: a NULL argument, n_tasks of 0 or above DPOW_BATCH_MAX, i_begin > i_end, a budget
+ * outside its range; DPOW_ERANGE: i_end > DPOW_K_LIMIT * 256, more than INT32_MAX entries);
+ * *launches_out = launches. */
+int dpow_scan_plan(const uint64_t *i_begin, const uint64_t *i_end, const uint32_t *ntz,
+                   size_t n_tasks, uint64_t cap, uint32_t capacity, dpow_batch_range *out,
+                   size_t max_entries, uint64_t *launches_out);
+/* What dpow_scan_batch does when a launch of `total` local indices and hit weight `weight`
+ * overflowed its list: the budgets (*cap_out local indices, *capacity_out / 4 hit weight, both
+ * arguments of dpow_scan_plan) it plans the same parts with again, each half of what the launch
+ * held, rounded up to a multiple of 256 (1024 for the capacity) and at least that.  A launch of
+ * 256 indices cannot overflow a list of at least 256 entries, and repeated halving gets there. */
+void dpow_scan_plan_halve(uint64_t total, uint64_t weight, uint64_t *cap_out, uint32_t *capacity_out);
 
 /* ---------------------------------------------------------------------------
  * Introspection / measurement.

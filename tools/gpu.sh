@@ -37,6 +37,9 @@
 #   census-many [reps]   the batched census's GPU tests, then its kernel's rate beside census_kernel's, its
 #                    tasks per second beside the looped census and where a call's time goes
 #                    (tools/census_many_rate.py -> census_many_rate.json)
+#   scan-many [reps]   the batched scan's GPU tests, then its kernel's rate beside scan_kernel's, its tasks
+#                    per second beside the looped scan and where a dense call's time goes
+#                    (tools/scan_many_rate.py -> scan_many_rate.json)
 #   digest [reps] [chunk-lib.so]   the digests' GPU tests, then the kernel's rate beside scan_kernel's, the host
 #                    call beside the host loops, the two stagings and the chunk sizes (tools/digest_rate.py ->
 #                    digest_rate.json); chunk-lib.so: a library built with EXTRA=-DDPOW_DIGEST_CHUNK_LOG2=20
@@ -139,6 +142,10 @@ census-many)
     timeout -k 10 300 python3 -u -m pytest tests/test_gpu_census_many.py -m gpu -x -v -s > $out/pytest_census_many.txt 2>&1 &&
     timeout -k 10 400 python3 -u tools/census_many_rate.py --reps "${1:-5}" --out $out/census_many_rate.json \
         > $out/census_many_rate.txt 2> $out/census_many_rate.err ;;
+scan-many)
+    timeout -k 10 300 python3 -u -m pytest tests/test_gpu_scan_many.py -m gpu -x -v -s > $out/pytest_scan_many.txt 2>&1 &&
+    timeout -k 10 400 python3 -u tools/scan_many_rate.py --reps "${1:-5}" --out $out/scan_many_rate.json \
+        > $out/scan_many_rate.txt 2> $out/scan_many_rate.err ;;
 digest)
     reps=${1:-5}; lib=()
     [ -n "$2" ] && lib=(--chunk-lib "$2")

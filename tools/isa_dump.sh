@@ -1,6 +1,6 @@
 #!/bin/bash
 # Device-only disassembly of every kernel translation unit of libdpow.so (the 8 (NBLK, SH) units,
-# the 2 chunk-length-spanning units, the segment-inner unit, search_ctrl.hip, the batch, the scan, the census, the batched census and the digest unit), one .s per unit, into DIR: a refactor of
+# the 2 chunk-length-spanning units, the segment-inner unit, search_ctrl.hip, the batch, the scan, the census, the batched census, the batched scan and the digest unit), one .s per unit, into DIR: a refactor of
 # the kernel sources that claims to change nothing is checked by diffing two dumps.
 #   bash tools/isa_dump.sh DIR [extra hipcc flags]
 set -e
@@ -28,5 +28,6 @@ unit batch md5_batch.hip "$@" &  # batch_kernel, queue_kernel and their upload k
 unit scan md5_scan.hip "$@" &    # scan_kernel
 unit census md5_census.hip "$@" &  # census_kernel
 unit census_many md5_census_many.hip "$@" &  # census_many_kernel
+unit scan_many md5_scan_many.hip "$@" &  # scan_many_kernel
 unit digest md5_digest.hip "$@" &  # digest_kernel
 wait
