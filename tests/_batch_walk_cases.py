@@ -1,6 +1,8 @@
 """Case families and the batched walk that pin the generic kernel of the batched search
 (csrc/md5_batch.hip) -- shared by tests/test_batch_walk_cases.py (CPU: the families are what they
 claim, from hashlib, the C oracle and the round planner alone) and tests/test_gpu_batch_walk.py.
+The depth reference and families F and G at the end serve the scan and census kernels as well
+(tests/test_listing_walk_cases.py on the CPU, tests/test_gpu_listing_walk.py on the GPU).
 
 Every expected value here comes from hashlib, the oracle or a committed fixture; nothing calls
 search_batch or search to learn an answer.  The builders are deterministic (SEED) and cached, so
@@ -378,3 +380,115 @@ def family_e(oracle, wbits):
 
 
 _family_e = {}
+
+
+# ---- the depth reference: every candidate of a window with its depth ----------------------------
+# The scan and the census (Miner.scan, scan_many, census, census_many) answer for a whole window in
+# one call, so tests/test_gpu_listing_walk.py compares them with these lists directly, no walk.
+D = 33   # depths 0..32 (DPOW_CENSUS_DEPTHS)
+
+
+@functools.lru_cache(maxsize=None)
+def window_depths(nonce, wb, wbits, k0, k1):
+    """((global index, depth), ...) of every candidate of a window in the reference's order (k
+    outer, thread byte inner), by hashlib alone; a candidate's depth is the number of trailing '0'
+    characters of its digest.  Cached per window."""
+    base, out = hashlib.md5(nonce), []
+    tbs = thread_bytes(wb, wbits)
+    for k in range(k0, k1):
+        chunk = secret_of(k << 8)[1:]
+        for tb in tbs:
+            h = base.copy()
+            h.update(bytes([tb]) + chunk)
+            x = h.hexdigest()
+            out.append((k << 8 | tb, len(x) - len(x.rstrip("0"))))
+    return tuple(out)
+
+
+def depths_of(c):
+    """window_depths of a case (EdgeCase) or a task."""
+    t = getattr(c, "task", c)
+    return window_depths(bytes(t.nonce), t.worker_byte, t.worker_bits, t.k_begin, t.k_end)
+
+
+def scan_hits_of(c, ntz):
+    """What Miner.scan returns for the case's window at N = ntz, from the depth reference."""
+    return [distpow.ScanHit(g, tz, secret_of(g)) for g, tz in depths_of(c) if tz >= ntz]
+
+
+def census_of(c):
+    """What Miner.census returns for the case's window, from the depth reference."""
+    count, first, tz = [0] * D, [None] * D, [0] * D
+    for g, t in depths_of(c):
+        for d in range(t + 1):
+            count[d] += 1
+            if first[d] is None:
+                first[d], tz[d] = g, t
+    return distpow.Census(tuple(count), tuple(first), tuple(tz), max((d for d in range(D) if count[d]), default=0))
+
+
+# ---- family F: wide partitions (worker_bits 0..2) at every edge and at the top -------------------
+F_WBITS = (0, 1, 2)
+F_SEED = SEED + 21   # (change the offset, not a threshold, if tests/test_listing_walk_cases.py's conditions fail)
+
+
+def f_positions(a):
+    """The p of family F at edge a: the block-count change itself, then one block for every chunk
+    length, the last one-block word, and two blocks for every chunk length.  At the top (chunks of
+    7 bytes) p = 54 - 7 = 47 is in the list already; p = 48 is the first that needs two blocks."""
+    return (48 if a == TOP else 54 - a, 0, 47, 55, 63)
+
+
+@functools.lru_cache(maxsize=None)
+def family_f():
+    """N = 1, worker_bits 0, 1 and 2 (256, 128 and 64 candidates per k): for every a = 0..7 and p of
+    f_positions(a), nonce lengths p and p + 64 on [max(edge(a) - 2, 0), edge(a) + 2), and on the
+    last three k below DPOW_K_LIMIT at the top.  240 tasks of at most 1024 candidates; at
+    worker_bits 0 the top windows end at local index 2^63 - 1."""
+    rnd = random.Random(F_SEED)
+    out = []
+    for a in range(8):
+        for wbits in F_WBITS:
+            for p in f_positions(a):
+                for nl in (p, p + 64):
+                    e = DPOW_K_LIMIT if a == TOP else edge(a)
+                    kb, ke = (DPOW_K_LIMIT - 3, DPOW_K_LIMIT) if a == TOP else (max(e - 2, 0), e + 2)
+                    t = BatchTask(_nonce(rnd, nl), 1, rnd.randrange(1 << wbits), wbits, kb, ke)
+                    out.append(EdgeCase(t, a, e, p))
+    return _fill_hits(out)
+
+
+# ---- family G: a partial wave whose clamped lanes need the second block --------------------------
+G_WBITS = (4, 5, 6, 7, 8)
+G_SEED = SEED + 22
+
+
+def _partial_wave_cases(rnd, with_edge):
+    """p = 54 - a, nonce lengths p and p + 64, worker_bits 4..8: [edge - d, edge + 1) (with_edge) or
+    [edge - d, edge) for d = 1..per - 2, per the k of a 64-lane wave; below edge(0) = 1 there is
+    k = 0 only, so there d = 1."""
+    out = []
+    for a in range(7):
+        for nl in (54 - a, 54 - a + 64):
+            for wbits in G_WBITS:
+                per = 64 >> (8 - wbits)
+                for d in range(1, 2 if a == 0 else per - 1):
+                    t = BatchTask(_nonce(rnd, nl), 1, rnd.randrange(1 << wbits), wbits, edge(a) - d,
+                                  edge(a) + (1 if with_edge else 0))
+                    out.append(EdgeCase(t, a, edge(a), nl % 64, d))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def family_g():
+    """N = 1: windows of fewer than 64 local indices that end with the first two-block k, edge(a).
+    A kernel hashes such a window in one partial wave from the window's begin: its lanes below the
+    edge need one block, the lanes of the edge's k two, and so do the inactive lanes, which are
+    clamped to the window's last index.  1378 tasks."""
+    return _fill_hits(_partial_wave_cases(random.Random(G_SEED), True))
+
+
+@functools.lru_cache(maxsize=None)
+def family_g_controls():
+    """Family G's windows without the edge's k: no lane, clamped or not, needs two blocks."""
+    return _fill_hits(_partial_wave_cases(random.Random(G_SEED + 1), False))
