@@ -1,7 +1,7 @@
 // dpow_api.cpp -- the C ABI (include/dpow.h) over the gfx950 search kernels: the context's
 // lifecycle (dpow_open, dpow_close), its accessors and stats, the argument-checking entry points
 // of the searches (dpow_search: search.cpp; dpow_search_batch: batch.cpp; dpow_scan: scan.cpp;
-// dpow_census_window: census.cpp; dpow_census_batch: census_many.cpp; dpow_scan_batch: scan_many.cpp; dpow_digests, dpow_digests_device: digests.cpp; dpow_search_bound) and the pure host helpers.  The node layer is node.cpp, the dpow_diag_* entry points diag.cpp.
+// dpow_census_window: census.cpp; dpow_census_batch: census_many.cpp; dpow_scan_batch: scan_many.cpp; dpow_digests, dpow_digests_device: digests.cpp; dpow_scan_device: scan_dev.cpp; dpow_search_bound) and the pure host helpers.  The node layer is node.cpp, the dpow_diag_* entry points diag.cpp.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -9,6 +9,7 @@
 
 #include <algorithm>
 
+#include "../../include/dpow_diag.h"
 #include "../../include/dpow_worker.h"
 #include "batch.h"
 #include "batch_engine.h"
@@ -19,6 +20,7 @@
 #include "md5_host.h"
 #include "md5_variants.h"
 #include "scan.h"
+#include "scan_dev.h"
 #include "scan_many.h"
 
 using namespace dpow;
@@ -188,6 +190,7 @@ void dpow_close(dpow_ctx *c) {
     census_many_free(c->census_many);
     scan_many_free(c->scan_many);
     digests_free(c->digests);
+    scan_dev_free(c->scan_dev);
     if (c->d_ctrl_alloc) (void)hipFree(c->d_ctrl_alloc);
     if (c->d_claims) (void)hipFree(c->d_claims);
     if (c->h_snap) (void)hipHostFree(c->h_snap);
@@ -315,6 +318,43 @@ int dpow_scan(dpow_ctx *c, const uint8_t *nonce, size_t nonce_len, uint32_t ntz,
     c->last_use.store(now_ns(), std::memory_order_relaxed);
     return scan_run(&c->scan, c->stream, c->h_cancel, nonce, nonce_len, ntz, worker_byte, worker_bits, k_begin, k_end,
                     out, max_hits, n_hits, k_done, stats);
+}
+
+int dpow_scan_device(dpow_ctx *c, const uint8_t *nonce, size_t nonce_len, uint32_t ntz, uint32_t worker_byte,
+                     uint32_t worker_bits, uint64_t k_begin, uint64_t k_end, void *d_idx_out, void *d_tz_out,
+                     size_t max_hits, size_t *n_hits, uint64_t *k_done, dpow_batch_stats *stats) {
+    if (!d_idx_out || !n_hits || !k_done) return set_error(DPOW_EINVAL, "dpow_scan_device: NULL argument");
+    if ((reinterpret_cast<uintptr_t>(d_idx_out) & 7u) != 0u)
+        return set_error(DPOW_EINVAL, "dpow_scan_device: indices not 8-byte aligned");
+    if (max_hits < DPOW_SCAN_DEVICE_MIN_HITS)
+        return set_error(DPOW_EINVAL, "dpow_scan_device: max_hits below 16384 (one workgroup's candidates)");
+    dpow_batch_task t{};  // the window's own errors first: they need no context
+    t.nonce = nonce;
+    t.nonce_len = nonce_len;
+    t.worker_byte = worker_byte;
+    t.k_begin = k_begin;
+    t.k_end = k_end;
+    const int rc = batch_check_task(t, "dpow_scan_device");
+    if (rc < 0) return rc;
+    if (!c) return set_error(DPOW_EINVAL, "dpow_scan_device: ctx is NULL");
+    if (c->node) return set_error(DPOW_EINVAL, "dpow_scan_device: a node slot is attached to the context");
+    *n_hits = 0;
+    *k_done = k_begin;
+    if (stats) *stats = dpow_batch_stats{};
+    if (k_begin == k_end) return DPOW_EXHAUSTED;  // (*k_done = k_end)
+    if (__atomic_load_n(c->h_cancel, __ATOMIC_ACQUIRE) != 0u) return DPOW_CANCELLED;  // raised on entry: no launch
+    const DeviceScope on_device(c->device);
+    if (on_device.e != hipSuccess) return hip_fail(on_device.e, "hipSetDevice");
+    c->last_use.store(now_ns(), std::memory_order_relaxed);
+    return scan_dev_run(&c->scan_dev, c->stream, c->h_cancel, nonce, nonce_len, ntz, worker_byte, worker_bits, k_begin,
+                        k_end, d_idx_out, d_tz_out, max_hits, n_hits, k_done, stats);
+}
+
+int dpow_diag_scan_device_times(dpow_ctx *c, double *mask_ms, double *place_ms, double *depth_ms) {
+    if (!c || !mask_ms || !place_ms || !depth_ms)
+        return set_error(DPOW_EINVAL, "dpow_diag_scan_device_times: NULL argument");
+    scan_dev_times(c->scan_dev, mask_ms, place_ms, depth_ms);
+    return 0;
 }
 
 int dpow_scan_batch(dpow_ctx *c, dpow_scan_task *tasks, size_t n_tasks, dpow_scan_hit *out, size_t max_hits,

@@ -15,6 +15,9 @@
 //   dpow_cli scan <nonce-hex> <ntz> <k_begin> <k_end> [worker_byte worker_bits [device]]
 //       every hit of the window (dpow_scan), one line per hit: its global index, its depth and its
 //       secret in hex
+//   dpow_cli scan-device <nonce-hex> <ntz> <k_begin> <k_end> [worker_byte worker_bits [device]]
+//       the window's hits left in device memory (dpow_scan_device), paged; one JSON line: the
+//       count, the first and the last hit (index, depth, secret) and the calls' time
 //   dpow_cli census <nonce-hex> <k_begin> <k_end> [worker_byte worker_bits [device]]
 //       how deep the window goes (dpow_census_window), one line per depth up to the deepest: the
 //       depth, the number of candidates at least that deep, the first one's global index and its
@@ -32,6 +35,7 @@
 //       time dpow_digest_of_index in a loop over 2^n sequential indices from 2^32 (no GPU): what a
 //       caller pays per entry on the host; one JSON line with the median of `reps` loops
 // Each other command prints one JSON line.
+#include <dlfcn.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -283,6 +287,90 @@ static int cmd_scan(int argc, char **argv) {
     return rc == DPOW_EXHAUSTED ? 0 : 1;
 }
 
+// The HIP runtime calls scan-device needs for its device buffers.  The harness is built without the
+// HIP headers; libdpow.so has the runtime loaded, so the symbols are looked up in the process.
+typedef int (*hip_malloc_fn)(void **, size_t);
+typedef int (*hip_free_fn)(void *);
+typedef int (*hip_set_device_fn)(int);
+typedef int (*hip_memcpy_fn)(void *, const void *, size_t, int);
+constexpr int kHipMemcpyDeviceToHost = 2;
+
+static int cmd_scan_device(int argc, char **argv) {
+    if (argc < 6) return 2;
+    std::vector<uint8_t> nonce = from_hex(argv[2]);
+    const uint32_t ntz = (uint32_t)atoi(argv[3]);
+    uint64_t k = strtoull(argv[4], nullptr, 0);
+    const uint64_t k_end = strtoull(argv[5], nullptr, 0);
+    const uint32_t wb = argc > 7 ? (uint32_t)atoi(argv[6]) : 0, wbits = argc > 7 ? (uint32_t)atoi(argv[7]) : 0;
+    const int dev = argc > 8 ? atoi(argv[8]) : 0;
+    dpow_ctx *ctx = nullptr;
+    int rc = dpow_open(dev, &ctx);
+    if (rc) return fail("dpow_open", rc);
+    const hip_malloc_fn dev_malloc = (hip_malloc_fn)dlsym(RTLD_DEFAULT, "hipMalloc");
+    const hip_free_fn dev_free = (hip_free_fn)dlsym(RTLD_DEFAULT, "hipFree");
+    const hip_memcpy_fn dev_memcpy = (hip_memcpy_fn)dlsym(RTLD_DEFAULT, "hipMemcpy");
+    const hip_set_device_fn dev_set = (hip_set_device_fn)dlsym(RTLD_DEFAULT, "hipSetDevice");
+    if (!dev_malloc || !dev_free || !dev_memcpy || !dev_set) {
+        fprintf(stderr, "scan-device: the HIP runtime's symbols are not visible in the process\n");
+        return 1;
+    }
+    if (dev_set(dev) != 0) {  // the buffers belong on the context's device
+        fprintf(stderr, "scan-device: hipSetDevice failed\n");
+        return 1;
+    }
+    const size_t page = 1u << 20;
+    void *d_idx = nullptr, *d_tz = nullptr;
+    if (dev_malloc(&d_idx, page * 8) != 0 || dev_malloc(&d_tz, page) != 0) {
+        fprintf(stderr, "scan-device: hipMalloc failed\n");
+        return 1;
+    }
+    // The first and the last entry of the window's list are the first of the first page that has
+    // one and the last of the last: two 9-byte copies per such page, whatever the page holds.
+    uint64_t total = 0, first = 0, last = 0;
+    uint8_t first_tz = 0, last_tz = 0;
+    uint32_t launches = 0, slices = 0;
+    double kernel_ms = 0.0;
+    const double t0 = now_s();
+    do {
+        size_t n = 0;
+        dpow_batch_stats st;
+        rc = dpow_scan_device(ctx, nonce.data(), nonce.size(), ntz, wb, wbits, k, k_end, d_idx, d_tz, page, &n, &k, &st);
+        if (rc < 0) return fail("dpow_scan_device", rc);
+        launches += st.launches;
+        slices += st.rounds;
+        kernel_ms += st.kernel_ms;
+        if (n == 0) continue;
+        int e = 0;
+        if (total == 0) {
+            e |= dev_memcpy(&first, d_idx, 8, kHipMemcpyDeviceToHost);
+            e |= dev_memcpy(&first_tz, d_tz, 1, kHipMemcpyDeviceToHost);
+        }
+        e |= dev_memcpy(&last, (const uint8_t *)d_idx + 8 * (n - 1), 8, kHipMemcpyDeviceToHost);
+        e |= dev_memcpy(&last_tz, (const uint8_t *)d_tz + (n - 1), 1, kHipMemcpyDeviceToHost);
+        if (e != 0) {
+            fprintf(stderr, "scan-device: hipMemcpy failed\n");
+            return 1;
+        }
+        total += n;
+    } while (rc == DPOW_MORE);
+    const double dt = now_s() - t0;
+    const auto hit_json = [](uint64_t g, uint8_t tz) {
+        uint8_t sec[DPOW_MAX_SECRET];
+        size_t len = 0;
+        dpow_secret_from_index(g, sec, &len);
+        return "{\"global_idx\":" + std::to_string(g) + ",\"tz\":" + std::to_string(tz) +
+               ",\"secret\":" + bytes_json(sec, len) + "}";
+    };
+    printf("{\"status\":%d,\"k_done\":%llu,\"hits\":%llu,\"first\":%s,\"last\":%s,\"slices\":%u,\"launches\":%u,"
+           "\"kernel_ms\":%.3f,\"ms\":%.3f}\n",
+           rc, (unsigned long long)k, (unsigned long long)total, total ? hit_json(first, first_tz).c_str() : "null",
+           total ? hit_json(last, last_tz).c_str() : "null", slices, launches, kernel_ms, dt * 1e3);
+    dev_free(d_idx);
+    dev_free(d_tz);
+    dpow_close(ctx);
+    return rc == DPOW_EXHAUSTED ? 0 : 1;
+}
+
 // One line per depth up to the deepest: the depth, its count, its first index and that secret in hex.
 static void print_census(const dpow_census &c) {
     for (uint32_t d = 0; d <= c.deepest && c.count_ge[d] > 0; ++d) {
@@ -466,6 +554,7 @@ int main(int argc, char **argv) {
     if (argc >= 2 && !strcmp(argv[1], "census")) return cmd_census(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "census-many")) return cmd_census_many(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "scan")) return cmd_scan(argc, argv);
+    if (argc >= 2 && !strcmp(argv[1], "scan-device")) return cmd_scan_device(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "scan-many")) return cmd_scan_many(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "batch")) return cmd_batch(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "mine")) return cmd_mine(argc, argv);
@@ -479,6 +568,7 @@ int main(int argc, char **argv) {
             "       dpow_cli latency [reps [device]]\n"
             "       dpow_cli batch <ntz> <nonce-hex> [<nonce-hex> ...] [--device N]\n"
             "       dpow_cli scan <nonce-hex> <ntz> <k_begin> <k_end> [worker_byte worker_bits [device]]\n"
+            "       dpow_cli scan-device <nonce-hex> <ntz> <k_begin> <k_end> [worker_byte worker_bits [device]]\n"
             "       dpow_cli scan-many <ntz> <k_begin> <k_end> <nonce-hex> [<nonce-hex> ...] [--device N]\n"
             "       dpow_cli census <nonce-hex> <k_begin> <k_end> [worker_byte worker_bits [device]]\n"
             "       dpow_cli census-many <k_begin> <k_end> <nonce-hex> [<nonce-hex> ...] [--device N]\n"

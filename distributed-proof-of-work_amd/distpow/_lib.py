@@ -103,6 +103,8 @@ class ScanHitC(ctypes.Structure):
                 ("secret", ctypes.c_uint8 * DPOW_MAX_SECRET)]
 
 
+SCAN_DEVICE_MIN_HITS = 16384  # dpow_scan_device: the least max_hits (include/dpow.h DPOW_SCAN_DEVICE_MIN_HITS)
+
 DIGEST_BAD_DEPTH = 0xFF  # dpow_digests_device: the depth byte of an entry beyond DPOW_K_LIMIT
 
 CENSUS_DEPTHS = 33  # depths 0..32 (include/dpow.h DPOW_CENSUS_DEPTHS)
@@ -326,6 +328,13 @@ def lib():
         "dpow_scan_plan": (ctypes.c_int, [u64p, u64p, u32p, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint32,
                                           ctypes.POINTER(BatchRange), ctypes.c_size_t, u64p]),
         "dpow_scan_plan_halve": (None, [ctypes.c_uint64, ctypes.c_uint64, u64p, u32p]),
+        "dpow_scan_device": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32,
+                                            ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, vp, vp,
+                                            ctypes.c_size_t, szp, u64p, ctypes.POINTER(BatchStats)]),
+        "dpow_scan_device_cut": (ctypes.c_size_t, [u32p, ctypes.c_size_t, ctypes.c_size_t]),
+        "dpow_diag_scan_device_times": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_double),
+                                                       ctypes.POINTER(ctypes.c_double),
+                                                       ctypes.POINTER(ctypes.c_double)]),
         "dpow_digests": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_size_t, vp, ctypes.c_size_t, vp, vp, szp,
                                         ctypes.POINTER(BatchStats)]),
         "dpow_digests_device": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_size_t, vp, ctypes.c_size_t, vp, vp,

@@ -18,7 +18,7 @@ from ._lib import (CANCELLED, DPOW_K_LIMIT, DPOW_MAX_SECRET, DPOW_NO_HIT, EXHAUS
 
 __all__ = ["Miner", "SearchResult", "BatchTask", "batch_candidate", "batch_plan", "batch_plan_block",
            "TaskQueue", "QueueResult", "queue_plan", "ScanHit", "scan_slice", "ScanTask", "scan_plan", "scan_plan_halve", "Census",
-           "CensusTask", "census_plan", "digest_of_index", "secret_from_index", "md5", "verify", "trailing_zero_nibbles",
+           "scan_device_cut", "CensusTask", "census_plan", "digest_of_index", "secret_from_index", "md5", "verify", "trailing_zero_nibbles",
            "thread_bytes", "remainder_bits", "global_index", "plan_window", "plan_candidate",
            "device_count", "DPOW_NO_HIT", "FOUND", "EXHAUSTED", "CANCELLED"]
 
@@ -186,6 +186,14 @@ class ScanHit:
 def scan_slice(num_trailing_zeros: int, capacity: int = _lib.SCAN_CAP) -> int:
     """Local indices per launch of a scan whose hit list holds `capacity` entries (dpow_scan_slice)."""
     return lib().dpow_scan_slice(num_trailing_zeros, capacity)
+
+
+def scan_device_cut(inclusive_prefix: Sequence[int], room: int) -> int:
+    """Leading workgroups of a slice whose hits fit `room`, given the inclusive prefix of the slice's
+    per-workgroup hit totals (dpow_scan_device_cut, the cut dpow_scan_device makes)."""
+    n = len(inclusive_prefix)
+    arr = (ctypes.c_uint32 * max(n, 1))(*inclusive_prefix)
+    return lib().dpow_scan_device_cut(arr, n, room)
 
 
 _SCAN_TASK_IN = struct.Struct("@PNIIIQQ")  # dpow_scan_task: the input fields
@@ -719,6 +727,69 @@ class Miner:
         if not (r == _lib.ERANGE and not strict):
             check(r, "dpow_digests_device")
         return dig, dep
+
+    # -- device scan ------------------------------------------------------------
+    def scan_cuda_page(self, nonce: Sequence[int], num_trailing_zeros: int, worker_byte: int = 0,
+                       worker_bits: int = 0, k_begin: int = 0, k_end: int = 1, max_hits: int = 1 << 20,
+                       want_depths: bool = True):
+        """One dpow_scan_device call: (status, idx, depths, k_done).  `idx` is a CUDA torch.int64
+        tensor of the hits' global indices in increasing order and `depths` a torch.uint8 tensor of
+        their depths (None unless want_depths), both on the context's device and of shape [n]: views
+        of the filled part of the call's max_hits-entry buffers, nothing crossing to the host.
+        EXHAUSTED: the window is done; MORE: these are all hits of [k_begin, k_done) and the caller
+        continues from k_done; CANCELLED likewise.  torch's current stream is synchronised before the
+        call, and the outputs are complete on return.  The call's launch counts are kept in
+        last_scan_device_stats (rounds: the slices; launches: every kernel launch)."""
+        import torch
+        nb = _b(nonce)
+        dev = torch.device("cuda", self.device)
+        idx = torch.empty((max(max_hits, 1),), dtype=torch.int64, device=dev)
+        dep = torch.empty((max(max_hits, 1),), dtype=torch.uint8, device=dev) if want_depths else None
+        cnt, k_done, st = ctypes.c_size_t(), ctypes.c_uint64(), _lib.BatchStats()
+        torch.cuda.current_stream(dev).synchronize()
+        r = check(lib().dpow_scan_device(self._ctx, nb, len(nb), num_trailing_zeros, worker_byte, worker_bits,
+                                         k_begin, k_end, idx.data_ptr(), dep.data_ptr() if want_depths else None,
+                                         max_hits, ctypes.byref(cnt), ctypes.byref(k_done), ctypes.byref(st)),
+                  "dpow_scan_device")
+        self.last_scan_device_stats = st
+        n = cnt.value
+        return r, idx[:n], dep[:n] if want_depths else None, k_done.value
+
+    def scan_cuda(self, nonce: Sequence[int], num_trailing_zeros: int, worker_byte: int = 0, worker_bits: int = 0,
+                  k_begin: int = 0, k_end: int = 1, max_hits: int = 1 << 20, want_depths: bool = True):
+        """(idx, depths) of every candidate of the partition over k in [k_begin, k_end) whose digest
+        ends in at least num_trailing_zeros '0' characters, in increasing global index, as CUDA
+        tensors (dpow_scan_device, paged over MORE and concatenated; max_hits is the page size).
+        `depths` is None unless want_depths.  A raised cancel flag ends the scan early with the hits
+        found so far (see `cancelled`; scan_cuda_page tells how far it got).  last_scan_device_stats
+        holds the sums over the pages."""
+        import torch
+        idxs, deps, total = [], [], _lib.BatchStats()
+        k = k_begin
+        while True:
+            r, idx, dep, k = self.scan_cuda_page(nonce, num_trailing_zeros, worker_byte, worker_bits, k, k_end,
+                                                 max_hits, want_depths)
+            st = self.last_scan_device_stats
+            total.launches += st.launches
+            total.rounds += st.rounds
+            total.candidates += st.candidates
+            total.kernel_ms += st.kernel_ms
+            idxs.append(idx)
+            deps.append(dep)
+            if r != _lib.MORE:
+                break
+        self.last_scan_device_stats = total
+        if len(idxs) == 1:
+            return idxs[0], deps[0]
+        return torch.cat(idxs), torch.cat(deps) if want_depths else None
+
+    def scan_device_times(self):
+        """(mask_ms, place_ms, depth_ms): the kernel time of the last dpow_scan_device call by kind
+        (dpow_diag_scan_device_times)."""
+        m, p, d = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+        check(lib().dpow_diag_scan_device_times(self._ctx, ctypes.byref(m), ctypes.byref(p), ctypes.byref(d)),
+              "dpow_diag_scan_device_times")
+        return m.value, p.value, d.value
 
     # -- measurement ------------------------------------------------------------
     def stats(self) -> Stats:

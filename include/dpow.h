@@ -38,7 +38,8 @@ extern "C" {
  * and so were the scan (dpow_scan, dpow_scan_slice, DPOW_MORE) and the census
  * (dpow_census_window, dpow_census_merge) and the digests (dpow_digests, dpow_digests_device,
  * dpow_digest_of_index) and the batched census (dpow_census_batch, dpow_census_plan) and the
- * batched scan (dpow_scan_batch, dpow_scan_plan, dpow_scan_plan_halve).
+ * batched scan (dpow_scan_batch, dpow_scan_plan, dpow_scan_plan_halve) and the device scan
+ * (dpow_scan_device, dpow_scan_device_cut, DPOW_SCAN_DEVICE_MIN_HITS).
  * A consumer built against another version must refuse the library before any
  * other call (distpow/_lib.py check_abi, tests/c/abi_harness.c). */
 #define DPOW_ABI_VERSION 5
@@ -257,6 +258,46 @@ int dpow_scan_batch(dpow_ctx *ctx, dpow_scan_task *tasks, size_t n_tasks,
                     dpow_scan_hit *out, size_t max_hits, size_t *n_out,
                     dpow_batch_stats *stats /* may be NULL */);
 /* (dpow_scan_plan, the call's launch planner, is with the host helpers below.) */
+
+/* ---------------------------------------------------------------------------
+ * Device scan (added within ABI 5): a window's hits in index order, left in device memory.
+ *
+ * dpow_scan's kernel appends hits in no order and its host sorts, re-hashes and copies every one,
+ * so a dense scan is host work (DESIGN.md sections 13 and 17).  dpow_scan_device answers the same
+ * question into caller-owned device memory: d_idx_out receives the global indices of the window's
+ * hits as uint64, in increasing order, and d_tz_out (may be NULL) the depth byte of each.  A
+ * caller goes on with dpow_digests_device, or with its own kernels, without the hits crossing to
+ * the host; the secret of an index is dpow_secret_from_index's.
+ *
+ * The order comes from the kernel's geometry, not from a sort (csrc/md5_scan_dev.hip, DESIGN.md
+ * section 18): one launch writes a slice's hit bitmap and per-workgroup hit totals, a second turns
+ * bitmap and prefix into the list, and the digest kernel (csrc/md5_digest.hip) computes the depths
+ * of the entries placed, which re-checks every verdict.  A slice is 2^28 candidates whatever ntz;
+ * the host reads one total per slice and no hit.  A last launch counts, over the whole list, the
+ * entries shallower than ntz or not above their predecessor, and the host recomputes 16 sampled
+ * entries with its own MD5: DPOW_EVERIFY if either fails.
+ *
+ * Returns DPOW_EXHAUSTED (0): the window is done, *k_done = k_end.  DPOW_MORE: the list is as full
+ * as whole workgroups' hits allow; it holds every hit of [k_begin, *k_done), and the caller goes on
+ * from *k_done.  A k's hits are never split, and a call that starts at k_begin always advances:
+ * a workgroup's range holds at most DPOW_SCAN_DEVICE_MIN_HITS hits, which is why max_hits below
+ * that is DPOW_EINVAL.  DPOW_CANCELLED: the context's cancel flag is raised (checked on entry,
+ * where it costs no launch, and between slices); the list holds every hit of [k_begin, *k_done).
+ * Argument errors are dpow_scan's, returned before any GPU work, plus DPOW_EINVAL for a NULL
+ * d_idx_out or one that is not 8-byte aligned; a context with a node slot attached is refused.
+ * ntz = 0 lists every candidate; ntz > 32 scans and lists none; an empty window is DPOW_EXHAUSTED
+ * without a launch.  The function returns after the context's stream has drained, so the outputs
+ * are complete on return.  It does not touch dpow_stats: stats->rounds = the slices (mask
+ * launches), stats->launches = every kernel launch of the call, stats->kernel_ms their durations.
+ * ------------------------------------------------------------------------- */
+#define DPOW_SCAN_DEVICE_MIN_HITS 16384
+int dpow_scan_device(dpow_ctx *ctx, const uint8_t *nonce, size_t nonce_len, uint32_t ntz,
+                     uint32_t worker_byte, uint32_t worker_bits, uint64_t k_begin, uint64_t k_end,
+                     void *d_idx_out /* max_hits uint64, 8-byte aligned */,
+                     void *d_tz_out  /* max_hits bytes, or NULL */,
+                     size_t max_hits, size_t *n_hits, uint64_t *k_done,
+                     dpow_batch_stats *stats /* may be NULL */);
+/* (dpow_scan_device_cut, the call's cut of a slice, is with the host helpers below.) */
 
 /* ---------------------------------------------------------------------------
  * Census (added within ABI 5): depth counts and per-depth first hits of a window in one pass.
@@ -754,6 +795,13 @@ int dpow_scan_plan(const uint64_t *i_begin, const uint64_t *i_end, const uint32_
  * held, rounded up to a multiple of 256 (1024 for the capacity) and at least that.  A launch of
  * 256 indices cannot overflow a list of at least 256 entries, and repeated halving gets there. */
 void dpow_scan_plan_halve(uint64_t total, uint64_t weight, uint64_t *cap_out, uint32_t *capacity_out);
+
+/* The device scan's cut (host logic of dpow_scan_device, exposed for testing; DESIGN.md section
+ * 18): given the inclusive prefix of a slice's per-workgroup hit totals (non-decreasing, n_groups
+ * entries) and the room left in the caller's list, the largest number of leading workgroups whose
+ * hits fit: n_groups when the slice's total fits, 0 when not even the first does (or for a NULL
+ * prefix). */
+size_t dpow_scan_device_cut(const uint32_t *inclusive_prefix, size_t n_groups, size_t room);
 
 /* ---------------------------------------------------------------------------
  * Introspection / measurement.

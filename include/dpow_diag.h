@@ -165,6 +165,12 @@ int dpow_diag_node_post_at(struct dpow_node_slot *slot, uint64_t global_idx, int
  * (round 6: the registry keeps one alias per device).  DPOW_EINVAL when no slot is attached. */
 int dpow_diag_node_alias(struct dpow_ctx *ctx, void **cached, void **lookup);
 
+/* The kernel time of ctx's last dpow_scan_device call by kind, in ms (tools/scan_device_rate.py):
+ * its mask launches (each stamps its own duration into its completion record), its place
+ * launches and its depth launches (HIP events around them).  Zeros before the first call.
+ * Returns 0, or DPOW_EINVAL for a NULL argument. */
+int dpow_diag_scan_device_times(struct dpow_ctx *ctx, double *mask_ms, double *place_ms, double *depth_ms);
+
 /* Environment knob (no entry point): DPOW_DIAG_BOARD_SPLIT=1 makes dpow_board_search run every
  * rank on its own partition even when all ranks share one GPU -- the multi-GPU role, for tests
  * on a one-GPU box (tests/test_coordinator.py). */

@@ -43,6 +43,9 @@
 #   digest [reps] [chunk-lib.so]   the digests' GPU tests, then the kernel's rate beside scan_kernel's, the host
 #                    call beside the host loops, the two stagings and the chunk sizes (tools/digest_rate.py ->
 #                    digest_rate.json); chunk-lib.so: a library built with EXTRA=-DDPOW_DIGEST_CHUNK_LOG2=20
+#   scan-device [reps]   the device scan's GPU tests, then its mask kernel's rate beside scan_kernel's, the
+#                    place launch's cost and its calls beside Miner.scan's (tools/scan_device_rate.py ->
+#                    scan_device_rate.json)
 set -o pipefail
 task=${1:?task}; tag=${2:?tag}; shift 2
 out=gpurun_out/$tag
@@ -152,6 +155,10 @@ digest)
     timeout -k 10 300 python3 -u -m pytest tests/test_gpu_digests.py -m gpu -x -v -s > $out/pytest_digests.txt 2>&1 &&
     timeout -k 10 500 python3 -u tools/digest_rate.py --reps "$reps" --out $out/digest_rate.json "${lib[@]}" \
         > $out/digest_rate.txt 2> $out/digest_rate.err ;;
+scan-device)
+    timeout -k 10 300 python3 -u -m pytest tests/test_gpu_scan_dev.py -m gpu -x -v -s > $out/pytest_scan_dev.txt 2>&1 &&
+    timeout -k 10 400 python3 -u tools/scan_device_rate.py --reps "${1:-5}" --out $out/scan_device_rate.json \
+        > $out/scan_device_rate.txt 2> $out/scan_device_rate.err ;;
 ab) timeout -k 10 800 python3 -u tools/ab_variants.py "$@" > $out/ab.log 2>&1 ;;
 node-ab)
     runs=$1; shift
