@@ -82,6 +82,14 @@ inline bool window_needs_no_launch(uint64_t k_begin, uint64_t k_end, uint64_t bo
     return k_begin >= k_end || (k_begin << 8) >= bound;
 }
 
+// The local index of global index g under the partition (rbits, base_tb), the inverse of
+// global_of_local; false when g's threadByte is another partition's (i is then meaningless).
+inline bool local_of_global(uint64_t g, uint32_t rbits, uint32_t base_tb, uint64_t &i) {
+    const uint32_t tb = (uint32_t)(g & 255u);
+    i = ((g >> 8) << rbits) | (tb & ((1u << rbits) - 1u));
+    return (tb >> rbits) == (base_tb >> rbits);
+}
+
 // One task after a launch that covered its local indices up to `cur` (of i_end) and left `best` in
 // out_best.  A value below the bound is a hit, re-verified with the host MD5.
 enum class Settled { kLive, kFound, kExhausted, kVerifyFailed };

@@ -92,19 +92,13 @@ int census_fold_launch(const char *who, uint8_t *msg, size_t nonce_len, uint32_t
         const uint64_t g = one.first_ge[d];
         if (g == DPOW_NO_HIT) continue;
         // The index is a candidate of this launch's range and partition.
-        const uint32_t tb = (uint32_t)(g & 255u);
-        const uint64_t i = ((g >> 8) << rbits) | (tb & ((1u << rbits) - 1u));
-        if ((tb >> rbits) != (base_tb >> rbits) || i < lo || i >= hi)
+        uint64_t i;
+        if (!local_of_global(g, rbits, base_tb, i) || i < lo || i >= hi)
             return set_error(DPOW_EVERIFY, w + ": kernel index outside its launch");
         if (d > 0 && g == one.first_ge[d - 1]) {
             one.first_tz[d] = one.first_tz[d - 1];
         } else {
-            uint8_t sec[DPOW_MAX_SECRET], dig[16];
-            size_t len = 0;
-            dpow_secret_from_index(g, sec, &len);
-            memcpy(msg + nonce_len, sec, len);
-            md5_digest(msg, nonce_len + len, dig);
-            one.first_tz[d] = digest_trailing_zero_nibbles(dig);
+            one.first_tz[d] = md5_depth_of_index(msg, nonce_len, g);
         }
         if (one.first_tz[d] < d) return set_error(DPOW_EVERIFY, w + ": kernel index failed host MD5 verification");
         one.deepest = d;

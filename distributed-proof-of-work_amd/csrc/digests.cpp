@@ -59,14 +59,6 @@ struct DigestSet {
     hipEvent_t done = nullptr;                   // behind the launch's last copy
 };
 
-void digest_of_index(size_t nonce_len, uint64_t g, uint8_t *msg, uint8_t digest[16], uint32_t *tz) {
-    // msg: nonce_len + DPOW_MAX_SECRET bytes of scratch that already starts with the nonce
-    size_t len = 0;
-    dpow_secret_from_index(g, msg + nonce_len, &len);
-    md5_digest(msg, nonce_len + len, digest);
-    *tz = digest_trailing_zero_nibbles(digest);
-}
-
 }  // namespace
 
 // The context's buffers.  Device: 64 control bytes, the out-of-range count (u32) at +0, zero between
@@ -245,8 +237,7 @@ int digests_run(DigestState **state, hipStream_t stream, const volatile uint32_t
         for (uint32_t q = 0; q < kDigestSamples; ++q) {
             const size_t j = (size_t)(count - 1) * q / (kDigestSamples - 1);
             uint8_t d[16];
-            uint32_t tz = 0;
-            digest_of_index(nonce_len, global_idx[first + j], msg.data(), d, &tz);
+            const uint32_t tz = md5_depth_of_index(msg.data(), nonce_len, global_idx[first + j], d);
             if ((digest_out && memcmp(h_digest + 16 * j, d, 16) != 0) || (tz_out && h_tz[j] != tz))
                 return fail(set_error(DPOW_EVERIFY, "dpow_digests: a sampled entry failed host MD5 verification"));
         }
@@ -319,8 +310,7 @@ extern "C" int dpow_digest_of_index(const uint8_t *nonce, size_t nonce_len, uint
     }
     if (nonce_len) memcpy(msg, nonce, nonce_len);
     uint8_t d[16];
-    uint32_t tz = 0;
-    dpow::digest_of_index(nonce_len, global_idx, msg, d, &tz);
+    const uint32_t tz = dpow::md5_depth_of_index(msg, nonce_len, global_idx, d);
     if (digest_out) memcpy(digest_out, d, 16);
     if (tz_out) *tz_out = tz;
     return 0;

@@ -11,7 +11,7 @@
 // nothing else.
 #pragma once
 
-#include "md5_batch.h"
+#include "md5_batch_dev.h"
 
 namespace dpow {
 
@@ -44,8 +44,7 @@ struct CensusLaunch {
 
 constexpr uint32_t kNoOff = 0xFFFFFFFFu;  // "no candidate yet" of a first-index offset (offsets are < kBatchMaxGroup)
 
-// One workgroup's range [lo, hi) of the task, with p / 4 a compile-time constant (md5_batch.h
-// batch_with_w0): 256 candidates per step, one per lane, in increasing index order.  First indices
+// One workgroup's range [lo, hi) of the task, with p / 4 a compile-time constant.  First indices
 // are kept as offsets from `lo` (32 bits) until the workgroup's flush.
 struct CensusGroup {
     const BatchTask *t;
@@ -54,35 +53,14 @@ struct CensusGroup {
 
     template <int W0>
     __device__ __forceinline__ void operator()() const {
-        const uint32_t p = t->p, rbits = t->rbits, base_tb = t->base_tb, len_bits = t->len_bits;
-        // the template and the midstate (wave-uniform: SGPRs)
-        uint32_t T[16], iv[4];
-#pragma unroll
-        for (int w = 0; w < 16; ++w) T[w] = t->T[w];
-#pragma unroll
-        for (int w = 0; w < 4; ++w) iv[w] = t->iv[w];
+        const BatchRow r = batch_load_row(t);
         // the wave's accumulators of depths 1..kCensusRare - 1 (wave-uniform: SGPRs)
         uint32_t cnt[kCensusRare - 1], first[kCensusRare - 1];
 #pragma unroll
         for (uint32_t l = 0; l + 1 < kCensusRare; ++l) cnt[l] = 0u, first[l] = kNoOff;
         const uint32_t rare_mask = tail_nibble_mask(kCensusRare);  // (folded: a constant)
         const uint32_t lane = threadIdx.x & 63u;
-        for (uint64_t i0 = lo + (threadIdx.x & ~63u); i0 < hi; i0 += kBlockThreads) {  // i0: the wave's first index
-            uint64_t i = i0 + lane;
-            const bool act = i < hi;
-            if (!act) i = hi - 1;
-            uint32_t M[32];
-            const uint32_t nblk = batch_candidate_words_at<W0>(T, p, rbits, base_tb, len_bits, i, M);
-            uint32_t st[4] = {iv[0], iv[1], iv[2], iv[3]};
-            batch_md5_block(st, M);
-            if constexpr (W0 > 11) {  // p + 1 + L > 55 needs p >= 48
-                if (__any(nblk == 2u)) {
-                    uint32_t s2[4] = {st[0], st[1], st[2], st[3]};
-                    batch_md5_block(s2, M + 16);
-#pragma unroll
-                    for (int w = 0; w < 4; ++w) st[w] = nblk == 2u ? s2[w] : st[w];
-                }
-            }
+        batch_window_steps<W0>(r, lo, hi, [&](uint64_t i0, uint64_t i, bool act, const uint32_t st[4]) {
             // (the ballot builtin on the compare itself: one v_cmp per mask, the active lanes' mask ANDed in)
             const unsigned long long active = __builtin_amdgcn_ballot_w64(act);
 #pragma unroll
@@ -106,7 +84,7 @@ struct CensusGroup {
                     }
                 }
             }
-        }
+        });
         // The wave's accumulators join the workgroup's table.
         if (lane == 0u) {
 #pragma unroll

@@ -16,18 +16,10 @@
 // agent-scope add and one guarded agent-scope atomicMin per depth with a non-zero count.  The
 // workgroups of one task, and of different tasks, meet nowhere else.
 //
-// Ordering: the form written at the top of md5_census.hip.  The table words are only ever touched
-// by 8-byte agent-scope atomics, which are performed at the device's coherence point and stay
-// counted in vmcnt until then.  Every wave drains (s_waitcnt vmcnt(0)) before the workgroup's
-// barrier and one lane then adds to the retirement count, so a workgroup's adds and mins are
-// performed before its retirement is counted.  The workgroup whose add completes the launch
-// acquires at agent scope, copies the tables of the launch's live-slot list to pinned memory --
-// entry q is the table of slot out_slots[q], as queue_kernel copies its best values -- with atomic
-// loads and relaxed system-scope stores, re-initialises those tables, and after a system-scope
-// release and a barrier re-zeroes the count and writes the completion record last.
-//
-// No wave waits for another wave or for the host: the grid is bounded, a workgroup's work is
-// fixed at its start, and the only cross-workgroup state is the tables and the retirement count.
+// Retirement (md5_batch_dev.h): the table words are only ever touched by 8-byte agent-scope
+// atomics, drained before the count.  The last workgroup copies the tables of the launch's
+// live-slot list to pinned memory -- entry q is the table of slot out_slots[q], as queue_kernel
+// copies its best values -- re-initialises those tables and writes the completion record.
 #include <hip/hip_runtime.h>
 
 #include "md5_census_many.h"
@@ -36,26 +28,13 @@ namespace dpow {
 
 namespace {
 
-// Retirement (md5_census.hip census_retire), with the copy-out of n_live tables by all four waves
-// of the last workgroup.  Word w of the copy is word w % kCensusTableWords of the table of slot
-// out_slots[w / kCensusTableWords].  A lane's kCopyUnroll slot loads are issued first, then its
-// kCopyUnroll table loads, then the stores, so that it waits for the slot list and for the
-// device's coherence point once per kCopyUnroll words, not once per word.
-constexpr uint32_t kCopyUnroll = 8;
-
+// The copy-out of n_live tables by all four waves of the last workgroup.  Word w of the copy is
+// word w % kCensusTableWords of the table of slot out_slots[w / kCensusTableWords].  A lane's
+// kCopyUnroll slot loads are issued first, then its kCopyUnroll table loads, then the stores, so
+// that it waits for the slot list, too, once per kCopyUnroll words.
 __device__ __forceinline__ void census_many_retire(const BatchLaunch &L, const uint32_t *__restrict__ out_slots,
                                                    uint32_t &s_last) {
-    asm volatile("s_waitcnt vmcnt(0) ; dpow census-many: adds and mins performed" ::: "memory");
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const uint32_t prev = __hip_atomic_fetch_add(L.done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_last = prev + 1u == L.n_blocks ? 1u : 0u;
-    }
-    __syncthreads();
-    if (s_last == 0u) return;  // (workgroup-uniform)
-    // The last workgroup: every other workgroup's adds and mins are performed.  Each wave acquires
-    // for its own loads; the loads are atomic (they bypass this CU's L1) as well.
+    if (!launch_count_retired<true>(L, s_last)) return;
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     const uint32_t n_words = L.n_live * kCensusTableWords;  // <= DPOW_BATCH_MAX * 66
     for (uint32_t w0 = threadIdx.x; w0 < n_words; w0 += kCopyUnroll * kBlockThreads) {
@@ -87,26 +66,15 @@ __device__ __forceinline__ void census_many_retire(const BatchLaunch &L, const u
             }
         }
     }
-    // every wave's copies before lane 0's record
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-    asm volatile("s_waitcnt vmcnt(0) ; dpow census-many: copies performed" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __hip_atomic_store(L.done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned long long t_start = __hip_atomic_load(L.t0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&L.rec->t_start, t_start, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(&L.rec->t_end, __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(&L.rec->seq, L.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    launch_copies_performed();
+    launch_write_record(L);
 }
 
 __global__ void __launch_bounds__(kBlockThreads)
     census_many_kernel(const BatchTask *__restrict__ tasks, const BatchEntry *__restrict__ blocks,
                        const uint32_t *__restrict__ out_slots, const BatchLaunch L) {
     __shared__ uint32_t s_cnt[kCensusDepths], s_first[kCensusDepths], s_last;
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        __hip_atomic_store(L.t0, __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    launch_start_tick(L);
     if (threadIdx.x < kCensusDepths) {
         s_cnt[threadIdx.x] = 0u;
         s_first[threadIdx.x] = kNoOff;

@@ -3,11 +3,9 @@
 //
 // One launch hashes D.n entries.  Workgroup b takes the b-th group of D.group entries, one entry per
 // lane and 256 per step.  The task row is a kernel argument, so its fields are wave-uniform scalar
-// loads; the message layout is data and a workgroup branches once on its wave-uniform p / 4
-// (md5_batch.h), so every byte position, every chunk length and both block counts go through the
-// same code as in batch_kernel.  What differs from the window kernels is that the lanes of a wave
-// hold unrelated candidates: the chunk length, and for p >= 48 the block count, vary per lane, which
-// the shared assembly already derives from the lane's own k.
+// loads; row and hash are the shared ones (md5_batch_dev.h).  What differs from the window kernels
+// is that the lanes of a wave hold unrelated candidates: the chunk length, and for p >= 48 the block
+// count, vary per lane, which the shared assembly already derives from the lane's own k.
 //
 // Each lane loads its own 8-byte index (a wave's 64 loads are one contiguous 512 bytes), range-
 // checks it, hashes, and stores the four state words as one 16-byte store and the depth as a byte.
@@ -24,6 +22,7 @@
 // fixed at its start.
 #include <hip/hip_runtime.h>
 
+#include "md5_batch_dev.h"
 #include "md5_digest.h"
 
 namespace dpow {
@@ -44,32 +43,15 @@ struct DigestGroup {
 
     template <int W0>
     __device__ __forceinline__ void operator()() const {
-        const uint32_t p = t->p, rbits = t->rbits, base_tb = t->base_tb, len_bits = t->len_bits;
-        // the template and the midstate (wave-uniform: SGPRs)
-        uint32_t T[16], iv[4];
-#pragma unroll
-        for (int w = 0; w < 16; ++w) T[w] = t->T[w];
-#pragma unroll
-        for (int w = 0; w < 4; ++w) iv[w] = t->iv[w];
+        const BatchRow r = batch_load_row(t);
         const uint32_t lane = threadIdx.x & 63u;
         for (uint32_t e0 = lo + (threadIdx.x & ~63u); e0 < hi; e0 += kBlockThreads) {  // e0: the wave's first entry
             const uint32_t e = e0 + lane;
             const bool act = e < hi;
             const unsigned long long g = act ? idx[e] : 0ull;
             const bool out_of_range = (g >> 8) >= kDigestKLimit;  // (never for a lane past the list)
-            uint32_t M[32];
-            const uint32_t nblk =
-                batch_candidate_words_at<W0>(T, p, rbits, base_tb, len_bits, out_of_range ? 0ull : g, M);
-            uint32_t st[4] = {iv[0], iv[1], iv[2], iv[3]};
-            batch_md5_block(st, M);
-            if constexpr (W0 > 11) {  // p + 1 + L > 55 needs p >= 48
-                if (__any(nblk == 2u)) {
-                    uint32_t s2[4] = {st[0], st[1], st[2], st[3]};
-                    batch_md5_block(s2, M + 16);
-#pragma unroll
-                    for (int w = 0; w < 4; ++w) st[w] = nblk == 2u ? s2[w] : st[w];
-                }
-            }
+            uint32_t st[4];
+            batch_hash_at<W0>(r, out_of_range ? 0ull : g, st);
             uint32_t depth = trailing_zero_nibbles(st[0], st[1], st[2], st[3]);
             if (out_of_range) {
                 st[0] = st[1] = st[2] = st[3] = 0u;

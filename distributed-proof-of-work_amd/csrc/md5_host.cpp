@@ -4,6 +4,7 @@
 // compression over the same constant tables the kernel uses.
 #include <string.h>
 
+#include "../../include/dpow.h"
 #include "dpow_common.h"
 #include "md5_host.h"
 
@@ -66,6 +67,15 @@ uint32_t digest_trailing_zero_nibbles(const uint8_t d[16]) {
         ++n;
     }
     return n;
+}
+
+uint32_t md5_depth_of_index(uint8_t *msg, size_t nonce_len, uint64_t g, uint8_t *digest, size_t *secret_len) {
+    size_t len = 0;
+    dpow_secret_from_index(g, msg + nonce_len, &len);
+    uint8_t d[16];
+    md5_digest(msg, nonce_len + len, digest ? digest : d);
+    if (secret_len) *secret_len = len;
+    return digest_trailing_zero_nibbles(digest ? digest : d);
 }
 
 }  // namespace dpow

@@ -2,33 +2,31 @@
 // bitmap and per-workgroup hit totals (scan_mask_kernel), the ordered list from bitmap and prefix
 // (scan_place_kernel), and the check of a finished call's list (scan_check_kernel).
 //
-// scan_mask_kernel.  The loop and the geometry are scan_kernel's (md5_scan.hip): workgroup b takes
-// the b-th group of L.group local indices of [i_begin, i_end), one candidate per lane and 256 per
-// step in increasing index order, the task row in the kernarg segment, one branch on the
-// wave-uniform p / 4.  The sink differs.  A wave's lanes hold the 64 consecutive local indices
-// i0 .. i0 + 63 and i0 - i_begin is a multiple of 64 (groups are multiples of 256), so the wave's
-// hit ballot is word (i0 - i_begin) / 64 of the slice's bitmap, hit or no hit, lanes past the range
-// contributing 0.  A wave runs at most 64 steps, so it keeps the words in one register pair -- step
-// s's ballot in lane s, put there by one compare and two selects with scalar operands, and only by
-// a step that has a candidate -- and its lanes store them behind the loop, one word each.  (One
-// lane storing every step's word as it comes is the same bitmap and cost the loop 1 %: DESIGN.md
-// section 18.)  A word is written for every wave-step the loop runs,
-// whatever it holds, so the bitmap is never zeroed: it holds stale words of earlier slices behind
-// this slice's ceil((i_end - i_begin) / 64), and nothing reads those.  The stores are plain: their
-// reader is a later launch.  Behind the loop each wave sums the bits of its words; the four sums meet
-// in LDS.  A step without a candidate costs the loop one scalar add more than scan_kernel's.
+// scan_mask_kernel.  The geometry is scan_kernel's (md5_scan.hip): workgroup b takes the b-th group
+// of L.group local indices of [i_begin, i_end), the task row in the kernarg segment; row, hash,
+// step loop and hit test are the shared ones (md5_batch_dev.h).  The sink differs.  A wave's lanes
+// hold the 64 consecutive local indices i0 .. i0 + 63 and i0 - i_begin is a multiple of 64 (groups
+// are multiples of 256), so the wave's hit ballot is word (i0 - i_begin) / 64 of the slice's
+// bitmap, hit or no hit, lanes past the range contributing 0.  A wave runs at most 64 steps, so it
+// keeps the words in one register pair -- step s's ballot in lane s, put there by one compare and
+// two selects with scalar operands, and only by a step that has a candidate -- and its lanes store them
+// behind the loop, one word each.  (One lane storing every step's word as it comes is the same
+// bitmap and cost the loop 1 %: DESIGN.md section 18.)  A word is written for every wave-step the
+// loop runs, whatever it holds, so the bitmap is never zeroed: it holds stale words of earlier
+// slices behind this slice's ceil((i_end - i_begin) / 64), and nothing reads those.  The stores
+// are plain: their reader is a later launch.  Behind the loop each wave sums the bits of its words;
+// the four sums meet in LDS.  A step without a candidate costs the loop one scalar add more than
+// scan_kernel's.
 //
-// Ordering within the mask launch (cdna_hip_programming.md 6, Guideline 16, form R1; md5_scan.hip
-// scan_retire): one lane publishes the workgroup's hit total with a 4-byte relaxed agent-scope
-// atomic store (write-through), every wave drains its stores (s_waitcnt vmcnt(0)) before the
-// workgroup's barrier, and one lane then adds to the retirement count -- the total is performed
-// before the retirement is counted, without an agent-scope release in every workgroup.  The
-// workgroup whose add completes the launch acquires once at agent scope, reads the totals with
-// agent-scope atomic loads (they bypass this CU's L1), and writes their inclusive prefix (at most
-// 16384 groups, uint32: a slice has at most 2^28 candidates) to a device array for the place launch
-// and the slice's total to pinned memory for the host; then it re-zeroes the retirement count and
-// writes the completion record.  (The host copies the prefix out itself when a slice does not fit
-// the caller's room: writing all of it to pinned memory in every launch cost more than the sink.)
+// Retirement (md5_batch_dev.h): one lane publishes the workgroup's hit total with a 4-byte relaxed
+// agent-scope atomic store, drained before the count.  The last workgroup reads the totals and
+// writes their inclusive prefix (at most 16384 groups, uint32: a slice has at most 2^28
+// candidates) to a device array for the place launch and the slice's total to pinned memory for
+// the host; then it writes the completion record.  It deviates in one thing: the total is lane 0's
+// own store and the prefix is read behind the kernel boundary, so nothing has to be ordered before
+// the record but lane 0's own stores.  (The host copies the prefix out itself when a slice does not
+// fit the caller's room: writing all of it to pinned memory in every launch cost more than the
+// sink.)
 //
 // scan_place_kernel.  A second bounded launch over the leading workgroups of the same slice.
 // Workgroup b loads the ceil((hi - lo) / 64) <= 256 bitmap words of its own range, one per thread,
@@ -49,14 +47,14 @@
 // check word.
 #include <hip/hip_runtime.h>
 
+#include "md5_batch_dev.h"
 #include "md5_scan_dev.h"
 
 namespace dpow {
 
 namespace {
 
-// One workgroup's range [lo, hi) of the task, with p / 4 a compile-time constant (md5_batch.h
-// batch_with_w0): 256 candidates per step, one per lane, in increasing index order.
+// One workgroup's range [lo, hi) of the task, with p / 4 a compile-time constant.
 struct ScanMaskGroup {
     const BatchTask *t;
     unsigned long long *mask;
@@ -65,14 +63,7 @@ struct ScanMaskGroup {
 
     template <int W0>
     __device__ __forceinline__ void operator()() const {
-        const uint32_t p = t->p, rbits = t->rbits, base_tb = t->base_tb, ntz = t->ntz, len_bits = t->len_bits;
-        const uint32_t dmask = t->dmask;
-        // the template and the midstate (wave-uniform: SGPRs)
-        uint32_t T[16], iv[4];
-#pragma unroll
-        for (int w = 0; w < 16; ++w) T[w] = t->T[w];
-#pragma unroll
-        for (int w = 0; w < 4; ++w) iv[w] = t->iv[w];
+        const BatchRow r = batch_load_row(t);
         const uint32_t lane = threadIdx.x & 63u;
         // The wave's words, gathered: lane s holds the ballot of the wave's step s (at most 64 steps:
         // a group is at most 64 x 256 indices), zero until a step with a hit puts its ballot there, and
@@ -81,34 +72,16 @@ struct ScanMaskGroup {
         // loop one scalar add.
         static_assert(kScanDevMaxGroup / kBlockThreads <= 64, "a wave's steps fit its lanes");
         uint32_t w_lo = 0u, w_hi = 0u, step = 0u;
-        for (uint64_t i0 = lo + (threadIdx.x & ~63u); i0 < hi; i0 += kBlockThreads) {  // i0: the wave's first index
-            uint64_t i = i0 + lane;
-            const bool act = i < hi;
-            if (!act) i = hi - 1;
-            uint32_t M[32];
-            const uint32_t nblk = batch_candidate_words_at<W0>(T, p, rbits, base_tb, len_bits, i, M);
-            uint32_t st[4] = {iv[0], iv[1], iv[2], iv[3]};
-            batch_md5_block(st, M);
-            if constexpr (W0 > 11) {  // p + 1 + L > 55 needs p >= 48
-                if (__any(nblk == 2u)) {
-                    uint32_t s2[4] = {st[0], st[1], st[2], st[3]};
-                    batch_md5_block(s2, M + 16);
-#pragma unroll
-                    for (int w = 0; w < 4; ++w) st[w] = nblk == 2u ? s2[w] : st[w];
-                }
-            }
-            const bool cand = act && (st[3] & dmask) == 0u;
-            if (__ballot(cand) != 0ull) {
-                const bool ok = cand && trailing_zero_nibbles(st[0], st[1], st[2], st[3]) >= ntz;
-                const unsigned long long m = __ballot(ok);
+        batch_window_steps<W0>(r, lo, hi, [&](uint64_t, uint64_t, bool act, const uint32_t st[4]) {
+            batch_hit_ballot(act, st, r.dmask, r.ntz, [&](unsigned long long m, bool) {
                 // The step's word of the bitmap (m and step are wave-uniform: scalar operands of one
                 // compare and two selects).
                 const bool keeper = lane == step;
                 w_lo = keeper ? (uint32_t)m : w_lo;
                 w_hi = keeper ? (uint32_t)(m >> 32) : w_hi;
-            }
+            });
             ++step;
-        }
+        });
         // The steps this wave ran: those whose first index lo + 64 wave + 256 s is below hi.  Step s's
         // word is (lo - i_begin) / 64 + 4 s + wave, below the slice's ceil((i_end - i_begin) / 64)
         // because hi <= i_end.  Every one of them is stored, hit or no hit.
@@ -147,17 +120,7 @@ __device__ __forceinline__ void scan_mask_retire(const ScanMaskLaunch &S, uint32
     if (threadIdx.x == 0)
         __hip_atomic_store(S.totals + blockIdx.x, s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3], __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0) ; dpow scan_dev: total performed" ::: "memory");
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const uint32_t prev = __hip_atomic_fetch_add(L.done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_last = prev + 1u == L.n_blocks ? 1u : 0u;
-    }
-    __syncthreads();
-    if (s_last == 0u) return;  // (workgroup-uniform)
-    // The last workgroup: every other workgroup's total is performed.  Each wave acquires for its own
-    // loads; the loads are atomic (they bypass this CU's L1) as well.
+    if (!launch_count_retired<true>(L, s_last)) return;
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     // A round takes 2048 totals, 8 consecutive ones per thread as four 8-byte loads in flight
     // together: 8 rounds for 16384 workgroups, where one total per thread and round was 64 rounds of
@@ -200,23 +163,16 @@ __device__ __forceinline__ void scan_mask_retire(const ScanMaskLaunch &S, uint32
     // 4-byte stores over the host link was the larger part of this tail: DESIGN.md section 18).
     if (threadIdx.x == 0)
         __hip_atomic_store(S.out_total, (unsigned long long)carry, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    // (The prefix stores need no order here: their readers are behind the kernel boundary.  The total
-    // and the record are lane 0's own, the record's store a system-scope release.)
-    if (threadIdx.x == 0) {
-        __hip_atomic_store(L.done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned long long t_start = __hip_atomic_load(L.t0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&L.rec->t_start, t_start, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(&L.rec->t_end, __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(&L.rec->seq, L.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    // (No launch_copies_performed: the prefix stores need no order here, their readers are behind the
+    // kernel boundary.  The total and the record are lane 0's own, the record's store a system-scope
+    // release.)
+    launch_write_record(L);
 }
 
 __global__ void __launch_bounds__(kBlockThreads) scan_mask_kernel(const ScanMaskLaunch S) {
     __shared__ uint32_t s_wave[4];
     __shared__ uint32_t s_last;
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        __hip_atomic_store(S.L.t0, __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    launch_start_tick(S.L);
     uint32_t wave_hits = 0u;
     uint64_t lo, hi;
     if (batch_block_range(S.i_begin, S.i_end, blockIdx.x, S.L.group, lo, hi)) {

@@ -46,12 +46,9 @@ uint64_t scan_slice(uint32_t ntz, uint32_t capacity) {
 
 bool scan_fill_hit(uint8_t *msg, size_t nonce_len, uint64_t g, uint32_t ntz, dpow_scan_hit &h) {
     size_t len = 0;
-    dpow_secret_from_index(g, h.secret, &len);
+    h.tz = md5_depth_of_index(msg, nonce_len, g, nullptr, &len);
+    memcpy(h.secret, msg + nonce_len, len);
     memset(h.secret + len, 0, DPOW_MAX_SECRET - len);
-    memcpy(msg + nonce_len, h.secret, len);
-    uint8_t d[16];
-    md5_digest(msg, nonce_len + len, d);
-    h.tz = digest_trailing_zero_nibbles(d);
     if (h.tz < ntz) return false;
     h.global_idx = g;
     h.secret_len = (uint32_t)len;
@@ -166,9 +163,8 @@ int scan_run(ScanState **state, hipStream_t stream, const volatile uint32_t *can
         for (size_t j = 0; j < hits.size(); ++j) {
             const uint64_t g = hits[j];
             // The entry is a candidate of this launch, and no other entry is the same one.
-            const uint32_t tb = (uint32_t)(g & 255u);
-            const uint64_t i = ((g >> 8) << rbits) | (tb & ((1u << rbits) - 1u));
-            if ((tb >> rbits) != (base_tb >> rbits) || (g >> 8) >= k_end || i < lo || i >= hi ||
+            uint64_t i;
+            if (!local_of_global(g, rbits, base_tb, i) || (g >> 8) >= k_end || i < lo || i >= hi ||
                 (j > 0 && hits[j - 1] == g))
                 return set_error(DPOW_EVERIFY, "dpow_scan: kernel entry outside its launch or listed twice");
             if ((g >> 8) != prev_k) {

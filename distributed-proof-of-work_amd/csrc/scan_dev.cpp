@@ -271,15 +271,11 @@ int scan_dev_run(ScanDevState **state, hipStream_t stream, const volatile uint32
         if (nonce_len) memcpy(msg.data(), nonce, nonce_len);
         for (uint32_t q = 0; q < kScanDevSamples; ++q) {
             const uint64_t g = smp[q].idx;
-            const uint32_t tb = (uint32_t)(g & 255u);
-            size_t len = 0;
-            uint8_t d[16];
-            bool ok = (tb >> rbits) == (base_tb >> rbits) && (g >> 8) >= k_begin && (g >> 8) < k_at &&
+            uint64_t i;
+            bool ok = local_of_global(g, rbits, base_tb, i) && (g >> 8) >= k_begin && (g >> 8) < k_at &&
                       (q == 0 || g >= smp[q - 1].idx);
             if (ok) {
-                dpow_secret_from_index(g, msg.data() + nonce_len, &len);
-                md5_digest(msg.data(), nonce_len + len, d);
-                const uint32_t tz = digest_trailing_zero_nibbles(d);
+                const uint32_t tz = md5_depth_of_index(msg.data(), nonce_len, g);
                 ok = tz >= ntz && (!tz_out || smp[q].tz == tz);
             }
             if (!ok) return set_error(DPOW_EVERIFY, "dpow_scan_device: a sampled entry failed host MD5 verification");

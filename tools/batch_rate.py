@@ -39,13 +39,17 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--kernel-rate-only", action="store_true",
+                    help="the kernel-rate section alone (an A/B of two builds needs nothing else)")
     ap.add_argument("--quick", action="store_true", help="N in {3, 5}, B in {1, 64} only")
     ap.add_argument("--rate-log2k", type=int, default=28)
     args = ap.parse_args()
     ns = [3, 5] if args.quick else [3, 4, 5, 6]
     bs = [1, 64] if args.quick else [1, 16, 64, 256, 1024]
+    if args.kernel_rate_only:
+        ns = []
     miner = distpow.Miner(0)
-    pool = [distpow.Miner(0) for _ in range(THREADS)]
+    pool = [distpow.Miner(0) for _ in range(0 if args.kernel_rate_only else THREADS)]
 
     def run_a(reqs):
         t0 = time.perf_counter()

@@ -37,6 +37,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--kernel-rate-only", action="store_true",
+                    help="the kernel-rate section alone (an A/B of two builds needs nothing else)")
     ap.add_argument("--rate-log2k", type=int, default=28)
     args = ap.parse_args()
     miner = distpow.Miner(0)
@@ -71,6 +73,14 @@ def main():
             "many_over_census_kernel": med(many_k) / med(one_k), "goal": 0.95,
             "census_many_kernel_ghs_all": many_k, "census_kernel_ghs_all": one_k}
     print(json.dumps({"kernel_rate": rate}), file=sys.stderr, flush=True)
+    if args.kernel_rate_only:
+        only = {"tool": "tools/census_many_rate.py", "reps": args.reps, "build_id": distpow.build_id(), "kernel_rate": rate}
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(json.dumps(only, indent=1) + "\n")
+        print(json.dumps(only))
+        miner.close()
+        return
 
     # -- tasks per second: one call beside the loop -------------------------------------------------
     tasks_tab = []

@@ -65,6 +65,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--kernel-rate-only", action="store_true",
+                    help="the kernel-rate section alone (an A/B of two builds needs nothing else)")
     ap.add_argument("--rate-log2k", type=int, default=28)
     ap.add_argument("--rare", action="append", default=[], metavar="N=LIB")
     args = ap.parse_args()
@@ -96,6 +98,14 @@ def main():
             "count_ge": list(c.count_ge[:c.deepest + 1]),
             "census_kernel_ghs_all": cen_k, "scan_kernel_ghs_all": scan_k}
     print(json.dumps({"census_rate": rate}), file=sys.stderr, flush=True)
+    if args.kernel_rate_only:
+        only = {"tool": "tools/census_rate.py", "reps": args.reps, "build_id": distpow.build_id(), "census_rate": rate}
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(json.dumps(only, indent=1) + "\n")
+        print(json.dumps(only))
+        miner.close()
+        return
 
     # -- kCensusRare at 2, 3 and 4 -----------------------------------------------------------------
     rare = {}

@@ -120,6 +120,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--kernel-rate-only", action="store_true",
+                    help="the kernel-rate section alone (an A/B of two builds needs nothing else)")
     ap.add_argument("--chunk-lib", default=None, help="a library built with EXTRA=-DDPOW_DIGEST_CHUNK_LOG2=20")
     ap.add_argument("--only-chunk", action="store_true", help="(the child run under --chunk-lib)")
     ap.add_argument("--only-outputs", action="store_true", help="measure the outputs section alone and add it to --out")
@@ -175,6 +177,14 @@ def main():
               "bytes_per_entry": 25, "digest_sequential_gbs": med(rate["sequential"]) * 25,
               "all": rate}
     print(json.dumps({"kernel": kernel}), file=sys.stderr, flush=True)
+    if args.kernel_rate_only:
+        only = {"tool": "tools/digest_rate.py", "reps": args.reps, "build_id": distpow.build_id(), "kernel": kernel}
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(json.dumps(only, indent=1) + "\n")
+        print(json.dumps(only))
+        miner.close()
+        return
     del lists, dig, dep
     torch.cuda.empty_cache()
 

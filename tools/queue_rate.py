@@ -185,6 +185,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--kernel-rate-only", action="store_true",
+                    help="M1's descriptor launch alone (an A/B of two builds needs nothing else)")
     ap.add_argument("--quick", action="store_true")
     args = ap.parse_args()
     bs = [1, 64] if args.quick else [1, 16, 64, 256, 1024]
@@ -192,8 +194,11 @@ def main():
     n_fresh = 100 if args.quick else 400
     out = {"tool": "tools/queue_rate.py", "build_id": distpow.build_id(), "reps": args.reps}
     with distpow.Miner(0) as miner:
-        out["m1_tasks_per_s"] = m1(miner, args.reps, bs)
+        if not args.kernel_rate_only:
+            out["m1_tasks_per_s"] = m1(miner, args.reps, bs)
         out["m1_descriptor_launch"] = m1_descriptors(miner, min(args.reps, 3))
+    if args.kernel_rate_only:
+        spreads = []
     out["m2_fresh_beside_old"] = []
     out["m3_fresh_after_previous_answer"] = []
     for s in spreads:

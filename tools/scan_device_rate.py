@@ -36,6 +36,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--kernel-rate-only", action="store_true",
+                    help="the kernel-rate section alone (an A/B of two builds needs nothing else)")
     ap.add_argument("--rate-log2k", type=int, default=28)
     args = ap.parse_args()
     miner = distpow.Miner(0)
@@ -92,6 +94,14 @@ def main():
             "scan_launches": ss.launches, "mask_over_scan_kernel": med(mask_k) / med(scan_k),
             "mask_kernel_ghs_all": mask_k, "scan_kernel_ghs_all": scan_k}
     print(json.dumps({"mask_rate": rate}), file=sys.stderr, flush=True)
+    if args.kernel_rate_only:
+        only = {"tool": "tools/scan_device_rate.py", "reps": args.reps, "build_id": distpow.build_id(), "mask_rate": rate}
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(json.dumps(only, indent=1) + "\n")
+        print(json.dumps(only))
+        miner.close()
+        return
 
     # -- the place launch beside the mask launch -----------------------------------------------------
     # (the sparse slice: 2^28 candidates of the len04 fixture's window around its one N >= 8 hit)
