@@ -2,11 +2,14 @@
 (csrc/md5_batch.hip) -- shared by tests/test_batch_walk_cases.py (CPU: the families are what they
 claim, from hashlib, the C oracle and the round planner alone) and tests/test_gpu_batch_walk.py.
 The depth reference and families F and G at the end serve the scan and census kernels as well
-(tests/test_listing_walk_cases.py on the CPU, tests/test_gpu_listing_walk.py on the GPU).
+(tests/test_listing_walk_cases.py on the CPU, tests/test_gpu_listing_walk.py on the GPU), and the
+device scan (tests/test_gpu_scan_dev_walk.py), whose geometry is restated behind them with family H,
+the windows that reach every group size of it.
 
 Every expected value here comes from hashlib, the oracle or a committed fixture; nothing calls
-search_batch or search to learn an answer.  The builders are deterministic (SEED) and cached, so
-a process computes each family once.
+search_batch or search to learn an answer (family H alone holds no hashes: its windows are too long
+for hashlib, and window_depths_cuda takes their depths from the digest kernel).  The builders are
+deterministic (SEED) and cached, so a process computes each family once.
 
 Notation: edge(a) = 256**a is the first k whose chunk is a + 1 bytes long; R = 256 >> worker_bits
 is the number of thread bytes per k; p = nonce_len % 64 is the byte the thread byte goes to; a
@@ -492,3 +495,145 @@ def family_g():
 def family_g_controls():
     """Family G's windows without the edge's k: no lane, clamped or not, needs two blocks."""
     return _fill_hits(_partial_wave_cases(random.Random(G_SEED + 1), False))
+
+
+# ---- the device scan's geometry, restated (csrc/scan_dev.cpp, batch.cpp batch_group) --------------
+# dpow_scan_device takes a window up in slices of SCAN_DEV_SLICE local indices from its begin; a slice
+# of `total` indices runs in workgroups of clamp(pow2_floor(total / SCAN_DEV_BLOCKS), SCAN_DEV_MIN_GROUP,
+# SCAN_DEV_MAX_GROUP) indices, the last one short.  tests/test_listing_walk_cases.py pins the four
+# constants to the sources; tests/test_gpu_scan_dev_walk.py pins the rule to the library's behaviour.
+SCAN_DEV_BLOCKS = 4096            # csrc/batch.h kBatchBlocks
+SCAN_DEV_MIN_GROUP = 256          # csrc/batch.h kBatchMinGroup
+SCAN_DEV_MAX_GROUP = 16384        # csrc/batch.h kBatchMaxGroup = csrc/md5_scan_dev.h kScanDevMaxGroup
+SCAN_DEV_SLICE = 1 << 28          # csrc/md5_scan_dev.h kScanDevSlice
+SCAN_DEV_STEP = 256               # local indices per workgroup step: four waves of 64 lanes
+SCAN_DEV_PREFIX_ROUND = 2048      # totals per round of the last workgroup's prefix: 8 per thread
+
+
+def scan_dev_geometry(total):
+    """(group, n_blocks) of a slice of `total` > 0 local indices."""
+    q = total // SCAN_DEV_BLOCKS
+    group = min(max(1 << (q.bit_length() - 1) if q else 0, SCAN_DEV_MIN_GROUP), SCAN_DEV_MAX_GROUP)
+    return group, -(-total // group)
+
+
+def scan_dev_slices(i_begin, i_end):
+    """[(lo, hi, group, n_blocks)] of the slices a call over the local indices [i_begin, i_end) runs."""
+    out, lo = [], i_begin
+    while lo < i_end:
+        hi = min(lo + SCAN_DEV_SLICE, i_end)
+        out.append((lo, hi) + scan_dev_geometry(hi - lo))
+        lo = hi
+    return out
+
+
+def scan_dev_wave_steps(n):
+    """[(steps, active lanes of the last step)] of the four waves of a workgroup whose range holds n
+    local indices: wave w's step s starts at offset 64 w + 256 s and runs when that is below n."""
+    out = []
+    for w in range(4):
+        first = 64 * w
+        steps = -(-(n - first) // SCAN_DEV_STEP) if first < n else 0
+        out.append((steps, min(n - first - SCAN_DEV_STEP * (steps - 1), 64) if steps else 0))
+    return out
+
+
+# ---- family H: every group size of the device scan, ragged across steps ---------------------------
+# No hashes: tests/test_gpu_scan_dev_walk.py takes the lists from the digest kernel (window_depths_cuda).
+H_SEED = SEED + 31
+H_WBITS, H_WB = 3, 5              # R = 32 candidates per k
+H_GROUPS = (512, 1024, 2048, 4096, 8192, 16384)
+
+
+@dataclass(frozen=True)
+class ScanWindow:
+    """A window of the device scan with the geometry it was built for."""
+    name: str
+    nonce: bytes
+    wb: int
+    wbits: int
+    k_begin: int
+    k_end: int
+    group: int           # of its one slice
+    n_blocks: int
+    s: int               # whole steps of the last group, before its ragged one (0: see the name)
+
+    @property
+    def rbits(self):
+        return 8 - self.wbits
+
+    @property
+    def total(self):
+        return (self.k_end - self.k_begin) << self.rbits
+
+
+def _scan_window(name, rnd, nonce, wb, wbits, total, group, n_blocks, s):
+    rbits = 8 - wbits
+    assert total % (1 << rbits) == 0
+    kb = rnd.randrange(1 << 16, 1 << 20) | 1          # odd: no multiple of group / R
+    return ScanWindow(name, nonce, wb, wbits, kb, kb + (total >> rbits), group, n_blocks, s)
+
+
+@functools.lru_cache(maxsize=None)
+def family_h():
+    """worker_bits 3 (R = 32), one worker byte, one 4-byte nonce: for each group g of H_GROUPS a window
+    of 4096 g + 256 s + 96 local indices (s = 1 for g = 512, else g / 512) -- 4097 workgroups, three
+    rounds of the prefix, a last group whose waves 0 and 1 run s + 1 steps, wave 1's last step half
+    full, and waves 2 and 3 run s; three windows at group 256 of 2047, 2048 and 2048.375 groups (one
+    round of the prefix not full, full, and a second round of one ragged group); and one window at
+    worker_bits 0 (R = 256, so no half wave: its last group is three whole steps of the four) with a
+    56-byte nonce, two final blocks, at group 1024; and one of 6145 groups of 512, four rounds of the
+    prefix, the last group ragged like g512's.  Every k_begin is odd."""
+    rnd = random.Random(H_SEED)
+    nonce = _nonce(rnd, 4)
+    out = []
+    for g in H_GROUPS:
+        s = 1 if g == 512 else g // 512
+        out.append(_scan_window(f"g{g}", rnd, nonce, H_WB, H_WBITS, 4096 * g + 256 * s + 96, g, 4097, s))
+    for name, total, n_blocks in (("b2047", 2047 * 256, 2047), ("b2048", 2048 * 256, 2048),
+                                  ("b2049r", 2048 * 256 + 96, 2049)):
+        out.append(_scan_window(name, rnd, nonce, H_WB, H_WBITS, total, 256, n_blocks, 0))
+    out.append(_scan_window("g1024w0n56", rnd, _nonce(rnd, 56), 0, 0, 4096 * 1024 + 768, 1024, 4097, 3))
+    # With 4097 workgroups the third round's carry reaches prefix[4096] alone, which no workgroup places
+    # from (only a page cut reads it): 6145 groups of 512 put a whole round and a fourth behind it.
+    out.append(_scan_window("g512b6145", rnd, nonce, H_WB, H_WBITS, 6144 * 512 + 256 + 96, 512, 6145, 1))
+    return tuple(out)
+
+
+def family_h_window(name):
+    return next(w for w in family_h() if w.name == name)
+
+
+@functools.lru_cache(maxsize=None)
+def second_slice_window():
+    """2^28 + 2^21 + 352 local indices at worker_bits 3: a whole slice at group 16384, then one of
+    4097 groups of 512, the last of 352 indices (group, n_blocks and s are the second slice's)."""
+    rnd = random.Random(H_SEED + 1)
+    return _scan_window("two-slices", rnd, _nonce(rnd, 4), H_WB, H_WBITS, (1 << 28) + (1 << 21) + 352, 512, 4097, 1)
+
+
+def window_indices_cuda(wb, wbits, k_begin, n, device, first=0):
+    """The global indices (k << 8 | thread byte, k outer) of the local offsets [first, first + n) of a
+    window from k_begin, built arithmetically on the device: a torch.int64 tensor."""
+    import torch
+    rbits = 8 - wbits
+    i = torch.arange(first, first + n, dtype=torch.int64, device=device)
+    return ((k_begin + (i >> rbits)) << 8) | (wb << rbits) | (i & ((1 << rbits) - 1))
+
+
+DIGEST_CHUNK = 1 << 22   # entries per digests_cuda call of the reference: a 64 MB digest tensor
+
+
+def window_depths_cuda(miner, nonce, wb, wbits, k_begin, k_end):
+    """The depth of every candidate of a window in index order, by the digest kernel
+    (Miner.digests_cuda over window_indices_cuda, DIGEST_CHUNK entries a call): a torch.uint8 tensor on
+    the miner's device.  The digest kernel gathers its candidates from a list, one per lane, and
+    shares the hash with the device scan's mask kernel but none of its geometry."""
+    import torch
+    total = (k_end - k_begin) << (8 - wbits)
+    dev = torch.device("cuda", miner.device)
+    out = torch.empty(total, dtype=torch.uint8, device=dev)
+    for first in range(0, total, DIGEST_CHUNK):
+        n = min(DIGEST_CHUNK, total - first)
+        out[first:first + n] = miner.digests_cuda(nonce, window_indices_cuda(wb, wbits, k_begin, n, dev, first))[1]
+    return out

@@ -18,6 +18,7 @@ import time
 import pytest
 import torch
 
+import _batch_walk_cases as W
 import distpow
 from distpow import CANCELLED, DPOW_K_LIMIT, EINVAL, ERANGE, EXHAUSTED, FOUND, MORE
 from test_gpu_scan import CASES, _nonce, _ref_cached, _reference, _secret_of, _thread_bytes
@@ -126,7 +127,14 @@ def test_paging_long_list_against_digests_and_census(miner):
     assert torch.equal(miner.digests_cuda(nonce, idx)[1], dep) and int(dep.min()) >= 1
     assert bool(((idx & 255) >> 5 == wb).all())
     assert idx.numel() == miner.census(nonce, wb, wbits, 0, k1).count_ge[1]
-    print(f"{idx.numel()} hits in {n_more + 1} pages, {t_scan:.3f} s")
+    # The depths above are the digest kernel's over the call's own entries, so they cannot see a hit at
+    # a wrong index.  This can: the digest kernel over every candidate of the window, listed
+    # arithmetically, and the entries are those of depth >= 1.
+    t = time.perf_counter()
+    every = W.window_depths_cuda(miner, nonce, wb, wbits, 0, k1)
+    assert every.numel() == k1 << 5
+    assert torch.equal(idx, W.window_indices_cuda(wb, wbits, 0, every.numel(), idx.device)[every >= 1])
+    print(f"{idx.numel()} hits in {n_more + 1} pages, {t_scan:.3f} s; the reference {time.perf_counter() - t:.3f} s")
 
 
 def test_slice_seams(miner):

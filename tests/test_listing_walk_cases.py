@@ -4,15 +4,25 @@ and the census's own planners -- shown from hashlib, the host copy of the kernel
 assembly (distpow.batch_candidate) and the planners (distpow.scan_plan, census_plan, scan_slice)
 alone, no GPU.  tests/test_gpu_listing_walk.py compares the scan and census kernels with these
 lists by equality, so a family that misses its edge, or a reference that is wrong, would pin
-nothing."""
+nothing.
+
+The device scan (tests/test_gpu_scan_dev_walk.py) runs the same sets, so the last tests show the same
+for it from a restatement of its geometry (_batch_walk_cases.scan_dev_geometry, pinned to the sources'
+constants here and to the library's behaviour on the GPU), and that family H, which holds no hashes,
+reaches every group size, the ragged last group and the prefix rounds it names."""
 import collections
+import os
+import re
 
 import distpow
 from distpow._lib import DPOW_BATCH_MAX, DPOW_K_LIMIT
 
 import _batch_walk_cases as W
+from test_gpu_listing_walk import IDS, SETS, _cases as set_cases
 
 MIN_GROUP = 256   # local indices of the smallest workgroup range (csrc/batch.h kBatchMinGroup)
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "distributed-proof-of-work_amd",
+                    "csrc")
 
 
 def _rbits(c):
@@ -174,3 +184,134 @@ def test_the_derived_references_agree():
             assert cen.count_ge[d] == len(at)
             assert (cen.first_ge[d], cen.first_tz[d]) == (at[0] if at else (None, 0))
         assert cen.merged(distpow.Census.empty()) == cen               # self-consistent by the library's own check
+
+
+# ---- the device scan (tests/test_gpu_scan_dev_walk.py) --------------------------------------------
+def _constant(header, name):
+    text = open(os.path.join(CSRC, header)).read()
+    m = re.search(r"\b%s\s*=\s*([^,;]+)[,;]" % name, text)
+    assert m, (header, name)
+    expr = re.sub(r"\b(\d+)(?:ull|u)\b", r"\1", m.group(1))
+    assert re.fullmatch(r"[\d\s<()]+", expr), expr                     # a number or a shift of numbers
+    return eval(expr)
+
+
+def test_scan_dev_geometry_constants_are_the_sources():
+    assert _constant("batch.h", "kBatchBlocks") == W.SCAN_DEV_BLOCKS == 4096
+    assert _constant("batch.h", "kBatchMinGroup") == W.SCAN_DEV_MIN_GROUP == 256
+    assert _constant("batch.h", "kBatchMaxGroup") == _constant("md5_scan_dev.h", "kScanDevMaxGroup") == \
+        W.SCAN_DEV_MAX_GROUP == 16384
+    assert _constant("md5_scan_dev.h", "kScanDevSlice") == _constant("batch.h", "kBatchCap") == W.SCAN_DEV_SLICE == 1 << 28
+    assert _constant("dpow_common.h", "kBlockThreads") == W.SCAN_DEV_STEP == 256
+    assert _constant("md5_scan_dev.hip", "kScanPrefixPer") * W.SCAN_DEV_STEP == W.SCAN_DEV_PREFIX_ROUND == 2048
+    # the rule itself: clamp(pow2_floor(total / 4096), 256, 16384), the last group short
+    src = open(os.path.join(CSRC, "batch.cpp")).read()
+    assert re.search(r"pow2_floor\(total / kBatchBlocks\), kBatchMinGroup\),\s*kBatchMaxGroup\)", src)
+    geo = W.scan_dev_geometry
+    assert [geo(t) for t in (1, 256, 257, (1 << 20) - 1)] == [(256, 1), (256, 1), (256, 2), (256, 4096)]
+    assert [geo(t)[0] for t in (1 << 20, (1 << 21) - 1, 1 << 21, 3 << 25, (1 << 26) - 1, 1 << 26, 1 << 28)] == \
+        [256, 256, 512, 16384, 8192, 16384, 16384]
+    assert geo(1 << 28) == (16384, 16384) and geo((1 << 21) + 352) == (512, 4097)
+    assert W.scan_dev_slices(7, 7) == [] and W.scan_dev_slices(32, (5 << 27) + 32) == \
+        [(32, (1 << 28) + 32, 16384, 16384), ((1 << 28) + 32, (2 << 28) + 32, 16384, 16384),
+         ((2 << 28) + 32, (5 << 27) + 32, 16384, 8192)]
+
+
+def test_every_edge_window_is_one_slice_of_small_groups_from_its_begin():
+    """The device scan's waves start at the slice's begin, and a slice at the call's: every window of
+    every family is one slice at group 256 of one to four workgroups, so its waves hold the local
+    indices the families were built round, as in the scan's and the census's descriptors above."""
+    seen = set()
+    for which in SETS:
+        for c in set_cases(which):
+            lo, hi = c.task.k_begin << _rbits(c), c.task.k_end << _rbits(c)
+            slices = W.scan_dev_slices(lo, hi)
+            assert len(slices) == 1 and slices[0][:3] == (lo, hi, MIN_GROUP), (which, c.task)
+            assert 1 <= slices[0][3] <= 4 and hi - lo <= 1024
+            seen.add(slices[0][3])
+    assert seen == {1, 2, 3, 4}
+
+
+def test_the_device_scan_tests_cannot_pass_vacuously():
+    """Per set of tests/test_gpu_scan_dev_walk.py: a window with a hit at N = 1 on each side of its
+    edge, where its windows have two sides (the controls of G end below the edge, and below
+    DPOW_K_LIMIT there is one side); at N = 3, a rate of 1/4096, over the sets together."""
+    deep = 0
+    for which, name in zip(SETS, IDS):
+        cases = set_cases(which)
+        deep += sum(1 for c in cases for _, tz in W.depths_of(c) if tz >= 3)
+        two_sided = [c for c in cases if c.task.k_begin < c.edge < c.task.k_end]
+        assert bool(two_sided) == (which[0] != "Gctl" and which != ("B", W.TOP) and which != ("F", W.TOP)), name
+        if two_sided:
+            assert any(any(h >> 8 < c.edge for h in c.hits) and any(h >> 8 >= c.edge for h in c.hits)
+                       for c in two_sided), name
+        else:
+            # (the controls at edge(0) are ten windows of k = 0 alone, 1 to 16 candidates each)
+            assert sum(len(c.hits) for c in cases) >= 1, name
+    print(f"{deep} candidates of depth >= 3 in the sets together")
+    assert deep >= 100
+
+
+def test_family_h_reaches_every_group_size_ragged_across_steps():
+    """From the restated geometry alone (nothing is hashed): each window is one slice of the group it
+    names; the g-windows have 4097 workgroups, odd and three rounds of the prefix (g512b6145: 6145 and
+    four), and a last group whose waves 0 and 1 run s + 1 steps, wave 1's last with 32 active lanes, and
+    waves 2 and 3 run s."""
+    fam = W.family_h()
+    assert [w.name for w in fam] == [f"g{g}" for g in W.H_GROUPS] + ["b2047", "b2048", "b2049r", "g1024w0n56", "g512b6145"]
+    assert W.H_GROUPS == (512, 1024, 2048, 4096, 8192, 16384)
+    assert len({w.nonce for w in fam}) == 2 and len({w.k_begin for w in fam}) == len(fam)
+    for w in fam:
+        R = 1 << w.rbits
+        lo, hi = w.k_begin << w.rbits, w.k_end << w.rbits
+        assert W.scan_dev_slices(lo, hi) == [(lo, hi, w.group, w.n_blocks)], w.name
+        assert w.k_begin != 0 and w.k_begin % max(w.group // R, 2) != 0 and w.k_end < 1 << 22
+        last = W.scan_dev_wave_steps(w.total - (w.n_blocks - 1) * w.group)
+        full = W.scan_dev_wave_steps(w.group)
+        assert full == [(w.group // 256, 64)] * 4
+        rounds = -(-w.n_blocks // W.SCAN_DEV_PREFIX_ROUND)
+        if w.name == "g1024w0n56":
+            assert (w.wbits, len(w.nonce), w.group, w.n_blocks, rounds) == (0, 56, 1024, 4097, 3)
+            assert w.total == 4096 * 1024 + 768 and last == [(3, 64)] * 4
+            assert distpow.batch_candidate(w.nonce, w.wb, w.wbits, lo)[2] == 2      # two final blocks
+            continue
+        assert (w.wbits, w.wb, len(w.nonce), R) == (3, W.H_WB, 4, 32)
+        if w.name.startswith("g"):
+            many = w.name == "g512b6145"       # the third round's carry reaches groups that are placed from
+            assert w.s == (1 if w.group == 512 else w.group // 512)
+            assert w.total == (6144 if many else 4096) * w.group + 256 * w.s + 96
+            assert (w.n_blocks, rounds, w.n_blocks % 2) == ((6145, 4, 1) if many else (4097, 3, 1))
+            assert last == [(w.s + 1, 64), (w.s + 1, 32), (w.s, 64), (w.s, 64)]
+            assert 2 <= w.group // 256 <= 64 and w.s + 1 <= w.group // 256     # the steps fit a wave's lanes
+        else:
+            assert w.group == 256 and w.total < 1 << 20
+            assert (w.n_blocks, w.total, rounds) == {"b2047": (2047, 2047 * 256, 1), "b2048": (2048, 2048 * 256, 1),
+                                                     "b2049r": (2049, 2048 * 256 + 96, 2)}[w.name]
+            assert last == ([(1, 64), (1, 32), (0, 0), (0, 0)] if w.name == "b2049r" else [(1, 64)] * 4)
+    # the window whose page cut falls inside its second slice
+    w = W.second_slice_window()
+    lo, hi = w.k_begin << w.rbits, w.k_end << w.rbits
+    assert W.scan_dev_slices(lo, hi) == [(lo, lo + (1 << 28), 16384, 16384), (lo + (1 << 28), hi, 512, 4097)]
+    assert w.total == (1 << 28) + (1 << 21) + 352 and (w.group, w.n_blocks) == (512, 4097)
+    assert W.scan_dev_wave_steps(352) == [(2, 64), (2, 32), (1, 64), (1, 64)]
+
+
+def test_second_slice_cuts_differ():
+    """tests/test_gpu_scan_dev_walk.py cuts the second slice with room for 0, 1 and 40 of its hits: by
+    hashlib over the slice's first 2^18 local indices (about 64 hits at N = 3), the slice begins with
+    empty groups, so a room of 0 advances without placing anything, and the three rooms end at two
+    different k at least."""
+    w = W.second_slice_window()
+    k2 = w.k_begin + ((1 << 28) >> w.rbits)
+    hits = W.window_hits(w.nonce, 3, w.wb, w.wbits, k2, k2 + ((1 << 18) >> w.rbits))
+    totals = collections.Counter(((g >> 8) - k2 << w.rbits | g & 31) // w.group for g in hits)
+    assert len(hits) > 40
+    cuts = []
+    for room in (0, 1, 40):
+        n_fit = s = 0
+        while s + totals[n_fit] <= room:
+            s += totals[n_fit]
+            n_fit += 1
+        cuts.append(n_fit)
+    print(f"{len(hits)} hits in the first 512 groups of the second slice; rooms 0, 1, 40 take {cuts} groups")
+    assert cuts[0] >= 1 and len(set(cuts)) >= 2 and max(cuts) < 512
