@@ -139,6 +139,7 @@ struct CensusManyState;  // census_many.h
 struct ScanManyState;  // scan_many.h
 struct DigestState;  // digests.h
 struct ScanDevState;  // scan_dev.h
+struct ScanManyDevState;  // scan_many_dev.h
 
 // The body of dpow_search (arguments checked): search.cpp.
 int search_window(dpow_ctx *c, const uint8_t *nonce, size_t nonce_len, uint32_t ntz, uint32_t worker_byte,
@@ -209,6 +210,7 @@ struct __attribute__((visibility("default"))) dpow_ctx {
     dpow::ScanManyState *scan_many = nullptr;  // buffers of dpow_scan_batch: allocated by the first call (scan_many.cpp)
     dpow::DigestState *digests = nullptr;  // buffers of dpow_digests: allocated by the first call (digests.cpp)
     dpow::ScanDevState *scan_dev = nullptr;  // buffers of dpow_scan_device: allocated by the first call (scan_dev.cpp)
+    dpow::ScanManyDevState *scan_many_dev = nullptr;  // buffers of dpow_scan_batch_device: allocated by the first call (scan_many_dev.cpp)
 };
 
 namespace dpow {

@@ -1,7 +1,7 @@
 // dpow_api.cpp -- the C ABI (include/dpow.h) over the gfx950 search kernels: the context's
 // lifecycle (dpow_open, dpow_close), its accessors and stats, the argument-checking entry points
 // of the searches (dpow_search: search.cpp; dpow_search_batch: batch.cpp; dpow_scan: scan.cpp;
-// dpow_census_window: census.cpp; dpow_census_batch: census_many.cpp; dpow_scan_batch: scan_many.cpp; dpow_digests, dpow_digests_device: digests.cpp; dpow_scan_device: scan_dev.cpp; dpow_search_bound) and the pure host helpers.  The node layer is node.cpp, the dpow_diag_* entry points diag.cpp.
+// dpow_census_window: census.cpp; dpow_census_batch: census_many.cpp; dpow_scan_batch: scan_many.cpp; dpow_digests, dpow_digests_device: digests.cpp; dpow_scan_device: scan_dev.cpp; dpow_scan_batch_device: scan_many_dev.cpp; dpow_search_bound) and the pure host helpers.  The node layer is node.cpp, the dpow_diag_* entry points diag.cpp.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -22,6 +22,7 @@
 #include "scan.h"
 #include "scan_dev.h"
 #include "scan_many.h"
+#include "scan_many_dev.h"
 
 using namespace dpow;
 
@@ -191,6 +192,7 @@ void dpow_close(dpow_ctx *c) {
     scan_many_free(c->scan_many);
     digests_free(c->digests);
     scan_dev_free(c->scan_dev);
+    scan_many_dev_free(c->scan_many_dev);
     if (c->d_ctrl_alloc) (void)hipFree(c->d_ctrl_alloc);
     if (c->d_claims) (void)hipFree(c->d_claims);
     if (c->h_snap) (void)hipHostFree(c->h_snap);
@@ -367,6 +369,19 @@ int dpow_scan_batch(dpow_ctx *c, dpow_scan_task *tasks, size_t n_tasks, dpow_sca
     if (on_device.e != hipSuccess) return hip_fail(on_device.e, "hipSetDevice");
     c->last_use.store(now_ns(), std::memory_order_relaxed);
     return scan_many_run(&c->scan_many, c->stream, c->h_cancel, tasks, n_tasks, out, max_hits, n_out, stats);
+}
+
+int dpow_scan_batch_device(dpow_ctx *c, dpow_scan_task *tasks, size_t n_tasks, void *d_idx_out, void *d_tz_out,
+                           void *d_row_out, size_t max_hits, size_t *n_out, dpow_batch_stats *stats) {
+    const int rc = scan_many_dev_check(tasks, n_tasks, d_idx_out, d_row_out, max_hits, n_out);  // the call's own errors first: they need no context
+    if (rc < 0) return rc;
+    if (!c) return set_error(DPOW_EINVAL, "dpow_scan_batch_device: ctx is NULL");
+    if (c->node) return set_error(DPOW_EINVAL, "dpow_scan_batch_device: a node slot is attached to the context");
+    const DeviceScope on_device(c->device);
+    if (on_device.e != hipSuccess) return hip_fail(on_device.e, "hipSetDevice");
+    c->last_use.store(now_ns(), std::memory_order_relaxed);
+    return scan_many_dev_run(&c->scan_many_dev, c->stream, c->h_cancel, tasks, n_tasks, d_idx_out, d_tz_out, d_row_out,
+                             max_hits, n_out, stats);
 }
 
 int dpow_census_window(dpow_ctx *c, const uint8_t *nonce, size_t nonce_len, uint32_t worker_byte,

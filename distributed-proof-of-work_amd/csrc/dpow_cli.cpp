@@ -25,6 +25,10 @@
 //   dpow_cli scan-many <ntz> <k_begin> <k_end> <nonce-hex> [<nonce-hex> ...] [--device N]
 //       every hit of the same window of every nonce in batched calls (dpow_scan_batch), one line
 //       per hit: the nonce's number (from 0), then `scan`'s line
+//   dpow_cli scan-many-device <ntz> <k_begin> <k_end> <nonce-hex> [<nonce-hex> ...] [--device N]
+//       the hits of the same window of every nonce left in device memory (dpow_scan_batch_device),
+//       paged; per nonce a line with its number, its count and its first and last hit (index, depth),
+//       then one JSON line with the total and the calls' time
 //   dpow_cli census-many <k_begin> <k_end> <nonce-hex> [<nonce-hex> ...] [--device N]
 //       the census of the same window of every nonce in one batched call (dpow_census_batch): per
 //       task a line "# <nonce-hex>" and then `census`'s lines
@@ -490,6 +494,113 @@ static int cmd_scan_many(int argc, char **argv) {
     return cancelled ? 1 : 0;
 }
 
+// Per nonce its number, its count and its first and last hit; then the call's JSON line.  The
+// unfinished tasks go in again from their k_done until every one is exhausted; of a page only the
+// first and the last entry of each task's segment cross to the host.
+static int cmd_scan_many_device(int argc, char **argv) {
+    if (argc < 6) return 2;
+    const uint32_t ntz = (uint32_t)atoi(argv[2]);
+    const uint64_t k_begin = strtoull(argv[3], nullptr, 0), k_end = strtoull(argv[4], nullptr, 0);
+    int dev = 0;
+    std::vector<std::vector<uint8_t>> nonces;
+    for (int i = 5; i < argc; ++i) {
+        if (!strcmp(argv[i], "--device") && i + 1 < argc) dev = atoi(argv[++i]);
+        else nonces.push_back(from_hex(argv[i]));
+    }
+    if (nonces.empty()) return 2;
+    dpow_ctx *ctx = nullptr;
+    int rc = dpow_open(dev, &ctx);
+    if (rc) return fail("dpow_open", rc);
+    const hip_malloc_fn dev_malloc = (hip_malloc_fn)dlsym(RTLD_DEFAULT, "hipMalloc");
+    const hip_free_fn dev_free = (hip_free_fn)dlsym(RTLD_DEFAULT, "hipFree");
+    const hip_memcpy_fn dev_memcpy = (hip_memcpy_fn)dlsym(RTLD_DEFAULT, "hipMemcpy");
+    const hip_set_device_fn dev_set = (hip_set_device_fn)dlsym(RTLD_DEFAULT, "hipSetDevice");
+    if (!dev_malloc || !dev_free || !dev_memcpy || !dev_set) {
+        fprintf(stderr, "scan-many-device: the HIP runtime's symbols are not visible in the process\n");
+        return 1;
+    }
+    const size_t page = 1u << 20;
+    void *d_idx = nullptr, *d_tz = nullptr;
+    if (dev_set(dev) != 0 || dev_malloc(&d_idx, page * 8) != 0 || dev_malloc(&d_tz, page) != 0) {
+        fprintf(stderr, "scan-many-device: hipSetDevice or hipMalloc failed\n");
+        return 1;
+    }
+    struct Seen {
+        uint64_t hits = 0, first = 0, last = 0;
+        uint8_t first_tz = 0, last_tz = 0;
+    };
+    std::vector<Seen> seen(nonces.size());
+    std::vector<uint64_t> k(nonces.size(), k_begin);
+    std::vector<size_t> todo(nonces.size());
+    for (size_t i = 0; i < todo.size(); ++i) todo[i] = i;
+    uint32_t launches = 0, rounds = 0, calls = 0;
+    double kernel_ms = 0.0;
+    bool cancelled = false;
+    const double t0 = now_s();
+    while (!todo.empty() && !cancelled) {
+        const size_t n_call = std::min<size_t>(todo.size(), DPOW_BATCH_MAX);
+        std::vector<dpow_scan_task> tasks(n_call);
+        for (size_t j = 0; j < n_call; ++j) {
+            memset(&tasks[j], 0, sizeof tasks[j]);
+            tasks[j].nonce = nonces[todo[j]].data();
+            tasks[j].nonce_len = nonces[todo[j]].size();
+            tasks[j].ntz = ntz;
+            tasks[j].k_begin = k[todo[j]];
+            tasks[j].k_end = k_end;
+        }
+        size_t n = 0;
+        dpow_batch_stats st;
+        rc = dpow_scan_batch_device(ctx, tasks.data(), n_call, d_idx, d_tz, nullptr, page, &n, &st);
+        if (rc < 0) return fail("dpow_scan_batch_device", rc);
+        launches += st.launches;
+        rounds += st.rounds;
+        kernel_ms += st.kernel_ms;
+        ++calls;
+        std::vector<size_t> next;
+        for (size_t j = 0; j < n_call; ++j) {
+            Seen &s = seen[todo[j]];
+            if (tasks[j].n_hits) {
+                const uint64_t a = tasks[j].first_hit, b = a + tasks[j].n_hits - 1;
+                int e = 0;
+                if (s.hits == 0) {
+                    e |= dev_memcpy(&s.first, (const uint8_t *)d_idx + 8 * a, 8, kHipMemcpyDeviceToHost);
+                    e |= dev_memcpy(&s.first_tz, (const uint8_t *)d_tz + a, 1, kHipMemcpyDeviceToHost);
+                }
+                e |= dev_memcpy(&s.last, (const uint8_t *)d_idx + 8 * b, 8, kHipMemcpyDeviceToHost);
+                e |= dev_memcpy(&s.last_tz, (const uint8_t *)d_tz + b, 1, kHipMemcpyDeviceToHost);
+                if (e != 0) {
+                    fprintf(stderr, "scan-many-device: hipMemcpy failed\n");
+                    return 1;
+                }
+                s.hits += tasks[j].n_hits;
+            }
+            k[todo[j]] = tasks[j].k_done;
+            if (tasks[j].status == DPOW_MORE) next.push_back(todo[j]);
+            cancelled = cancelled || tasks[j].status == DPOW_CANCELLED;
+        }
+        next.insert(next.end(), todo.begin() + n_call, todo.end());
+        todo.swap(next);
+    }
+    const double dt = now_s() - t0;
+    uint64_t total = 0;
+    for (size_t i = 0; i < seen.size(); ++i) {
+        const Seen &s = seen[i];
+        total += s.hits;
+        if (s.hits)
+            printf("%zu %llu %llu %u %llu %u\n", i, (unsigned long long)s.hits, (unsigned long long)s.first, s.first_tz,
+                   (unsigned long long)s.last, s.last_tz);
+        else
+            printf("%zu 0\n", i);
+    }
+    printf("{\"tasks\":%zu,\"hits\":%llu,\"calls\":%u,\"mask_launches\":%u,\"launches\":%u,\"kernel_ms\":%.3f,"
+           "\"ms\":%.3f}\n",
+           seen.size(), (unsigned long long)total, calls, rounds, launches, kernel_ms, dt * 1e3);
+    dev_free(d_idx);
+    dev_free(d_tz);
+    dpow_close(ctx);
+    return cancelled ? 1 : 0;
+}
+
 static int cmd_digest(int argc, char **argv) {
     if (argc < 4) return 2;
     std::vector<uint8_t> nonce = from_hex(argv[2]);
@@ -556,6 +667,7 @@ int main(int argc, char **argv) {
     if (argc >= 2 && !strcmp(argv[1], "scan")) return cmd_scan(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "scan-device")) return cmd_scan_device(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "scan-many")) return cmd_scan_many(argc, argv);
+    if (argc >= 2 && !strcmp(argv[1], "scan-many-device")) return cmd_scan_many_device(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "batch")) return cmd_batch(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "mine")) return cmd_mine(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "sweep")) return cmd_sweep(argc, argv);
@@ -570,6 +682,7 @@ int main(int argc, char **argv) {
             "       dpow_cli scan <nonce-hex> <ntz> <k_begin> <k_end> [worker_byte worker_bits [device]]\n"
             "       dpow_cli scan-device <nonce-hex> <ntz> <k_begin> <k_end> [worker_byte worker_bits [device]]\n"
             "       dpow_cli scan-many <ntz> <k_begin> <k_end> <nonce-hex> [<nonce-hex> ...] [--device N]\n"
+            "       dpow_cli scan-many-device <ntz> <k_begin> <k_end> <nonce-hex> [<nonce-hex> ...] [--device N]\n"
             "       dpow_cli census <nonce-hex> <k_begin> <k_end> [worker_byte worker_bits [device]]\n"
             "       dpow_cli census-many <k_begin> <k_end> <nonce-hex> [<nonce-hex> ...] [--device N]\n"
             "       dpow_cli digest <nonce-hex> <idx> [idx ...] [--device N]\n"

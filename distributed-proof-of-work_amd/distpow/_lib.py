@@ -335,6 +335,11 @@ def lib():
         "dpow_diag_scan_device_times": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_double),
                                                        ctypes.POINTER(ctypes.c_double),
                                                        ctypes.POINTER(ctypes.c_double)]),
+        "dpow_scan_batch_device": (ctypes.c_int, [vp, ctypes.POINTER(ScanTaskC), ctypes.c_size_t, vp, vp, vp,
+                                                  ctypes.c_size_t, szp, ctypes.POINTER(BatchStats)]),
+        "dpow_scan_batch_device_settle": (ctypes.c_int, [ctypes.POINTER(BatchRange), ctypes.c_size_t, u64p, u64p,
+                                                         ctypes.c_size_t, u64p, u32p, u32p, ctypes.c_int32,
+                                                         ctypes.POINTER(ctypes.c_int32)]),
         "dpow_digests": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_size_t, vp, ctypes.c_size_t, vp, vp, szp,
                                         ctypes.POINTER(BatchStats)]),
         "dpow_digests_device": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_size_t, vp, ctypes.c_size_t, vp, vp,

@@ -18,7 +18,7 @@ from ._lib import (CANCELLED, DPOW_K_LIMIT, DPOW_MAX_SECRET, DPOW_NO_HIT, EXHAUS
 
 __all__ = ["Miner", "SearchResult", "BatchTask", "batch_candidate", "batch_plan", "batch_plan_block",
            "TaskQueue", "QueueResult", "queue_plan", "ScanHit", "scan_slice", "ScanTask", "scan_plan", "scan_plan_halve", "Census",
-           "scan_device_cut", "CensusTask", "census_plan", "digest_of_index", "secret_from_index", "md5", "verify", "trailing_zero_nibbles",
+           "scan_device_cut", "scan_batch_device_settle", "CensusTask", "census_plan", "digest_of_index", "secret_from_index", "md5", "verify", "trailing_zero_nibbles",
            "thread_bytes", "remainder_bits", "global_index", "plan_window", "plan_candidate",
            "device_count", "DPOW_NO_HIT", "FOUND", "EXHAUSTED", "CANCELLED"]
 
@@ -194,6 +194,25 @@ def scan_device_cut(inclusive_prefix: Sequence[int], room: int) -> int:
     n = len(inclusive_prefix)
     arr = (ctypes.c_uint32 * max(n, 1))(*inclusive_prefix)
     return lib().dpow_scan_device_cut(arr, n, room)
+
+
+def scan_batch_device_settle(blocks, n_fit: int, i_begin: Sequence[int], i_end: Sequence[int], i_done: Sequence[int],
+                             next_row: int = 0, unfinished: int = _lib.MORE):
+    """What the first `n_fit` workgroup descriptors of a launch having been placed means for the tasks
+    of a dpow_scan_batch_device call (dpow_scan_batch_device_settle): (i_done, next_row, row_block,
+    status).  `blocks` is the launch's descriptors (BatchRange entries, as census_plan returns them);
+    the tasks have local index ranges [i_begin[i], i_end[i]) and progress i_done[i] before the launch.
+    row_block[j] is the descriptor whose place in the list is task j's row pointer, None for a task
+    this launch does not settle."""
+    n = len(i_begin)
+    arr = (_lib.BatchRange * max(n_fit, 1))(*blocks[:n_fit])
+    ib, ie, idn = ((ctypes.c_uint64 * max(n, 1))(*v) for v in (i_begin, i_end, i_done))
+    nr = ctypes.c_uint32(next_row)
+    rb = (ctypes.c_uint32 * max(n, 1))()
+    st = (ctypes.c_int32 * max(n, 1))()
+    check(lib().dpow_scan_batch_device_settle(arr, n_fit, ib, ie, n, idn, ctypes.byref(nr), rb, unfinished, st),
+          "dpow_scan_batch_device_settle")
+    return (list(idn)[:n], nr.value, [None if b == 0xFFFFFFFF else b for b in list(rb)[:n]], list(st)[:n])
 
 
 _SCAN_TASK_IN = struct.Struct("@PNIIIQQ")  # dpow_scan_task: the input fields
@@ -790,6 +809,101 @@ class Miner:
         check(lib().dpow_diag_scan_device_times(self._ctx, ctypes.byref(m), ctypes.byref(p), ctypes.byref(d)),
               "dpow_diag_scan_device_times")
         return m.value, p.value, d.value
+
+    # -- batched device scan ----------------------------------------------------
+    def scan_batch_cuda(self, tasks: Sequence[ScanTask], max_hits: int = 1 << 20, want_depths: bool = True,
+                        want_rows: bool = True):
+        """One dpow_scan_batch_device call: (results, idx, depths, rows).  `results` is one
+        (status, k_done) per task, as scan_batch's.  `idx` is a CUDA torch.int64 tensor of the hits'
+        global indices, task after task and within a task in increasing order, `depths` a torch.uint8
+        tensor of their depths (None unless want_depths) and `rows` a torch.int64 tensor of
+        len(tasks) + 1 row pointers (None unless want_rows): task i's hits are
+        idx[rows[i]:rows[i + 1]].  All are on the context's device, views of the call's buffers, no
+        hit crossing to the host; last_scan_many_device_rows holds the rows as a host list, from the
+        task structs.  The task that does not fit `max_hits` is MORE from its k_done, the tasks behind
+        it MORE from their k_begin.  torch's current stream is synchronised before the call, and the
+        outputs are complete on return.  The call's launch counts are kept in
+        last_scan_many_device_stats (rounds: the mask launches; launches: every kernel launch)."""
+        import torch
+        n = len(tasks)
+        arr = (_lib.ScanTaskC * max(n, 1))()
+        nonces = [_b(t.nonce) for t in tasks]
+        buf = ctypes.create_string_buffer(b"".join(nonces), max(sum(map(len, nonces)), 1))  # alive for the call
+        addr = ctypes.addressof(buf)
+        raw = (ctypes.c_ubyte * ctypes.sizeof(arr)).from_buffer(arr)
+        for j, (t, nb) in enumerate(zip(tasks, nonces)):
+            _SCAN_TASK_IN.pack_into(raw, j * _SCAN_TASK.size, addr, len(nb), t.num_trailing_zeros, t.worker_byte,
+                                    t.worker_bits, t.k_begin, t.k_end)
+            addr += len(nb)
+        dev = torch.device("cuda", self.device)
+        idx = torch.empty((max(max_hits, 1),), dtype=torch.int64, device=dev)
+        dep = torch.empty((max(max_hits, 1),), dtype=torch.uint8, device=dev) if want_depths else None
+        rows = torch.empty((n + 1,), dtype=torch.int64, device=dev) if want_rows else None
+        cnt, st = ctypes.c_size_t(), _lib.BatchStats()
+        torch.cuda.current_stream(dev).synchronize()
+        check(lib().dpow_scan_batch_device(self._ctx, arr, n, idx.data_ptr(), dep.data_ptr() if want_depths else None,
+                                           rows.data_ptr() if want_rows else None, max_hits, ctypes.byref(cnt),
+                                           ctypes.byref(st)), "dpow_scan_batch_device")
+        self.last_scan_many_device_stats = st
+        fields = list(_SCAN_TASK.iter_unpack(ctypes.string_at(arr, n * _SCAN_TASK.size)))
+        self.last_scan_many_device_rows = [f[9] for f in fields] + [cnt.value]
+        return ([(f[8], f[7]) for f in fields], idx[:cnt.value], dep[:cnt.value] if want_depths else None, rows)
+
+    def scan_many_cuda(self, tasks: Sequence[ScanTask], max_hits: int = 1 << 20, want_depths: bool = True):
+        """(idx, depths, rows) of every hit of many windows as CUDA tensors (dpow_scan_batch_device,
+        the unfinished tasks submitted again from their k_done over MORE and the pages concatenated
+        per task; max_hits is the page size): idx[rows[i]:rows[i + 1]] and the same slice of `depths`
+        (None unless want_depths) are what scan_cuda returns for tasks[i].  A raised cancel flag ends
+        it early with the hits found so far (see `cancelled`).  last_scan_many_device_stats holds the
+        sums over the calls."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        total = _lib.BatchStats()
+        todo = list(range(len(tasks)))
+        k = [t.k_begin for t in tasks]
+        pages = []  # (the call's tasks, its idx, its depths, its rows on the host)
+        first = None
+        while todo:
+            batch = todo[:_lib.DPOW_BATCH_MAX]  # at most DPOW_BATCH_MAX tasks per call
+            out = self.scan_batch_cuda(
+                [ScanTask(tasks[i].nonce, tasks[i].num_trailing_zeros, tasks[i].worker_byte, tasks[i].worker_bits,
+                          k[i], tasks[i].k_end) for i in batch], max_hits, want_depths)
+            res, idx, dep, rows = out
+            first = first or out
+            st = self.last_scan_many_device_stats
+            total.launches += st.launches
+            total.rounds += st.rounds
+            total.candidates += st.candidates
+            total.kernel_ms += st.kernel_ms
+            pages.append((batch, idx, dep, self.last_scan_many_device_rows))
+            for j, i in enumerate(batch):
+                k[i] = res[j][1]
+            if any(r == CANCELLED for r, _ in res):
+                break
+            todo = [i for i, (r, _) in zip(batch, res) if r == _lib.MORE] + todo[len(batch):]
+        self.last_scan_many_device_stats = total
+        if len(pages) == 1 and len(pages[0][0]) == len(tasks):  # one call did everything: its own outputs
+            return first[1], first[2], first[3]
+        seg_idx: List[list] = [[] for _ in tasks]
+        seg_dep: List[list] = [[] for _ in tasks]
+        counts = [0] * len(tasks)
+        for batch, idx, dep, r_host in pages:
+            for j, i in enumerate(batch):
+                if r_host[j + 1] > r_host[j]:
+                    seg_idx[i].append(idx[r_host[j]:r_host[j + 1]])
+                    if want_depths:
+                        seg_dep[i].append(dep[r_host[j]:r_host[j + 1]])
+                    counts[i] += r_host[j + 1] - r_host[j]
+        row_list = [0]
+        for c in counts:
+            row_list.append(row_list[-1] + c)
+        flat_idx = [s for segs in seg_idx for s in segs]
+        flat_dep = [s for segs in seg_dep for s in segs]
+        idx_all = torch.cat(flat_idx) if flat_idx else torch.empty((0,), dtype=torch.int64, device=dev)
+        dep_all = None
+        if want_depths:
+            dep_all = torch.cat(flat_dep) if flat_dep else torch.empty((0,), dtype=torch.uint8, device=dev)
+        return idx_all, dep_all, torch.tensor(row_list, dtype=torch.int64, device=dev)
 
     # -- measurement ------------------------------------------------------------
     def stats(self) -> Stats:

@@ -39,7 +39,8 @@ extern "C" {
  * (dpow_census_window, dpow_census_merge) and the digests (dpow_digests, dpow_digests_device,
  * dpow_digest_of_index) and the batched census (dpow_census_batch, dpow_census_plan) and the
  * batched scan (dpow_scan_batch, dpow_scan_plan, dpow_scan_plan_halve) and the device scan
- * (dpow_scan_device, dpow_scan_device_cut, DPOW_SCAN_DEVICE_MIN_HITS).
+ * (dpow_scan_device, dpow_scan_device_cut, DPOW_SCAN_DEVICE_MIN_HITS) and the batched device
+ * scan (dpow_scan_batch_device, dpow_scan_batch_device_settle).
  * A consumer built against another version must refuse the library before any
  * other call (distpow/_lib.py check_abi, tests/c/abi_harness.c). */
 #define DPOW_ABI_VERSION 5
@@ -298,6 +299,56 @@ int dpow_scan_device(dpow_ctx *ctx, const uint8_t *nonce, size_t nonce_len, uint
                      size_t max_hits, size_t *n_hits, uint64_t *k_done,
                      dpow_batch_stats *stats /* may be NULL */);
 /* (dpow_scan_device_cut, the call's cut of a slice, is with the host helpers below.) */
+
+/* ---------------------------------------------------------------------------
+ * Batched device scan (added within ABI 5): the hits of many windows left in device memory, in
+ * CSR order.
+ *
+ * dpow_scan_batch's task array in, dpow_scan_device's output form out.  Each task is a
+ * dpow_scan_task as dpow_scan_batch takes it, and the tasks are worked in array order.  Task i's
+ * hits are d_idx_out[first_hit .. first_hit + n_hits): uint64 global indices in strictly increasing
+ * order, exactly the indices dpow_scan_device writes for that task on an idle context; d_tz_out (may
+ * be NULL) holds the depth byte of each.  The tasks' segments are contiguous and in array order and
+ * *n_out is the total.  d_row_out (may be NULL: a context-owned array serves) receives the n_tasks
+ * + 1 row pointers: d_row_out[i] is task i's first_hit and d_row_out[n_tasks] is *n_out; the array
+ * does not descend, and an empty task, or one not begun, has the row of the next one.  The task
+ * structs' first_hit and n_hits come from the same array, copied out once per call: the host's work
+ * is O(tasks), never O(hits).
+ *
+ * The launches are dpow_census_batch's (2^28 local indices of the tasks taken together, whatever
+ * ntz: the list has no capacity of its own), each a mask launch whose total the host reads and,
+ * behind it without a wait, a rows, a place and a depth launch (csrc/md5_scan_many_dev.hip,
+ * DESIGN.md section 20).  The depth launch re-checks every entry placed -- a candidate of its
+ * workgroup descriptor, above its predecessor within the task, and, when depths are asked for, as
+ * deep as its task's ntz by an independent hash -- and the host recomputes 16 sampled entries with
+ * its own MD5 and their task's nonce: DPOW_EVERIFY if either fails.
+ *
+ * Returns 0 with every task's status set, or a negative code with no task written: dpow_scan_batch's
+ * argument errors, and DPOW_EINVAL for a NULL d_idx_out or n_out, a d_idx_out or d_row_out that is
+ * not 8-byte aligned, or max_hits < DPOW_SCAN_DEVICE_MIN_HITS; all of these before any GPU work
+ * (stats may be NULL); a context with a node slot attached is refused.  On 0 a finished task is
+ * DPOW_EXHAUSTED with k_done = k_end.  Paging: when the room ends the list is cut at a whole
+ * workgroup descriptor, a multiple of 256 local indices from the task's begin and hence a k boundary
+ * in every partition, so a k's hits are never split.  The task the cut falls in is DPOW_MORE at that k
+ * with its hits so far complete, every later task is DPOW_MORE with k_done = k_begin and no hits,
+ * and a cut that falls exactly on a task's first descriptor leaves the task before it
+ * DPOW_EXHAUSTED.  A descriptor holds at most DPOW_SCAN_DEVICE_MIN_HITS hits, so the first
+ * unfinished task advances in every call.  The cancel flag follows dpow_scan_batch: raised on entry,
+ * every task is DPOW_CANCELLED with k_done = k_begin without a launch; between launches, the tasks
+ * finished by then are DPOW_EXHAUSTED, the task a launch boundary cut is DPOW_CANCELLED at a whole k
+ * with its hits so far complete, the tasks not begun are DPOW_CANCELLED with k_done = k_begin.
+ * ntz = 0 lists every candidate and ntz > 32 none; a call whose tasks are all empty makes no launch
+ * and allocates nothing, but still writes the rows.  The function returns after the context's stream
+ * has drained.  It does not touch dpow_stats: stats->rounds = the mask launches, stats->launches =
+ * every kernel launch of the call, stats->kernel_ms their durations.
+ * ------------------------------------------------------------------------- */
+int dpow_scan_batch_device(dpow_ctx *ctx, dpow_scan_task *tasks, size_t n_tasks,
+                           void *d_idx_out  /* max_hits uint64, 8-byte aligned */,
+                           void *d_tz_out   /* max_hits bytes, or NULL */,
+                           void *d_row_out  /* n_tasks + 1 uint64, 8-byte aligned, or NULL */,
+                           size_t max_hits, size_t *n_out,
+                           dpow_batch_stats *stats /* may be NULL */);
+/* (dpow_scan_batch_device_settle, what a launch means for the tasks, is with the host helpers below.) */
 
 /* ---------------------------------------------------------------------------
  * Census (added within ABI 5): depth counts and per-depth first hits of a window in one pass.
@@ -802,6 +853,26 @@ void dpow_scan_plan_halve(uint64_t total, uint64_t weight, uint64_t *cap_out, ui
  * hits fit: n_groups when the slice's total fits, 0 when not even the first does (or for a NULL
  * prefix). */
 size_t dpow_scan_device_cut(const uint32_t *inclusive_prefix, size_t n_groups, size_t room);
+
+/* What a launch means for the tasks (host logic of dpow_scan_batch_device, exposed for testing;
+ * DESIGN.md section 20): the first n_fit workgroup descriptors of a launch (entries of
+ * dpow_census_plan, local indices; only task, i_begin and i_end are read) have been placed.  The
+ * tasks have local index ranges [i_begin[i], i_end[i]) and progress i_done[i] (in: before the launch;
+ * out: after it): each placed descriptor must begin where its task's progress stands and moves it
+ * to its own end.  *next_row (in/out) is the first task whose row pointer no earlier launch has
+ * settled.  A placed descriptor that begins its task settles that task's row and those of the
+ * (empty) tasks from *next_row up to it: row_block[j] = that descriptor's index in the launch, the
+ * row being the list's length before the launch plus the launch's hits before that descriptor;
+ * row_block[j] = 0xFFFFFFFF for every task this launch does not settle.  status[i] =
+ * DPOW_EXHAUSTED where i_done[i] == i_end[i] (an empty task is), else `unfinished` (DPOW_MORE or
+ * DPOW_CANCELLED when the call ends with this launch).  Returns the number of rows settled, or
+ * DPOW_EINVAL (nothing written) for a NULL argument, n_tasks of 0 or above DPOW_BATCH_MAX, n_fit
+ * above 20480, progress outside its task, or a descriptor that names no task, reaches beyond its
+ * task or does not begin at its task's progress. */
+int dpow_scan_batch_device_settle(const dpow_batch_range *blocks, size_t n_fit,
+                                  const uint64_t *i_begin, const uint64_t *i_end, size_t n_tasks,
+                                  uint64_t *i_done, uint32_t *next_row, uint32_t *row_block,
+                                  int32_t unfinished, int32_t *status);
 
 /* ---------------------------------------------------------------------------
  * Introspection / measurement.

@@ -46,6 +46,10 @@
 #   scan-device [reps]   the device scan's GPU tests, then its mask kernel's rate beside scan_kernel's, the
 #                    place launch's cost and its calls beside Miner.scan's (tools/scan_device_rate.py ->
 #                    scan_device_rate.json)
+#   scan-many-device [reps]   the batched device scan's GPU tests, then its mask kernel's rate beside
+#                    scan_many_kernel's, its calls beside Miner.scan_many's and Miner.scan_cuda's in a loop and
+#                    the call's host time against hits and tasks (tools/scan_many_device_rate.py ->
+#                    scan_many_device_rate.json)
 set -o pipefail
 task=${1:?task}; tag=${2:?tag}; shift 2
 out=gpurun_out/$tag
@@ -159,6 +163,10 @@ scan-device)
     timeout -k 10 300 python3 -u -m pytest tests/test_gpu_scan_dev.py -m gpu -x -v -s > $out/pytest_scan_dev.txt 2>&1 &&
     timeout -k 10 400 python3 -u tools/scan_device_rate.py --reps "${1:-5}" --out $out/scan_device_rate.json \
         > $out/scan_device_rate.txt 2> $out/scan_device_rate.err ;;
+scan-many-device)
+    timeout -k 10 300 python3 -u -m pytest tests/test_gpu_scan_many_dev.py -m gpu -x -v -s > $out/pytest_scan_many_dev.txt 2>&1 &&
+    timeout -k 10 500 python3 -u tools/scan_many_device_rate.py --reps "${1:-5}" --out $out/scan_many_device_rate.json \
+        > $out/scan_many_device_rate.txt 2> $out/scan_many_device_rate.err ;;
 ab) timeout -k 10 800 python3 -u tools/ab_variants.py "$@" > $out/ab.log 2>&1 ;;
 node-ab)
     runs=$1; shift
