@@ -140,6 +140,7 @@ struct ScanManyState;  // scan_many.h
 struct DigestState;  // digests.h
 struct ScanDevState;  // scan_dev.h
 struct ScanManyDevState;  // scan_many_dev.h
+struct DigestManyState;  // digests_many.h
 
 // The body of dpow_search (arguments checked): search.cpp.
 int search_window(dpow_ctx *c, const uint8_t *nonce, size_t nonce_len, uint32_t ntz, uint32_t worker_byte,
@@ -211,6 +212,7 @@ struct __attribute__((visibility("default"))) dpow_ctx {
     dpow::DigestState *digests = nullptr;  // buffers of dpow_digests: allocated by the first call (digests.cpp)
     dpow::ScanDevState *scan_dev = nullptr;  // buffers of dpow_scan_device: allocated by the first call (scan_dev.cpp)
     dpow::ScanManyDevState *scan_many_dev = nullptr;  // buffers of dpow_scan_batch_device: allocated by the first call (scan_many_dev.cpp)
+    dpow::DigestManyState *digests_many = nullptr;  // buffers of dpow_digests_batch and dpow_digests_batch_device: allocated by the first call (digests_many.cpp)
 };
 
 namespace dpow {

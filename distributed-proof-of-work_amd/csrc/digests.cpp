@@ -21,6 +21,7 @@
 // dpow_digest_of_index's code and compares every output the caller asked for; a mismatch is
 // DPOW_EVERIFY.  dpow_digests_device verifies nothing: its data never reaches the host.
 #include "digests.h"
+#include "digests_sets.h"
 
 #include <stdlib.h>
 #include <string.h>
@@ -44,20 +45,6 @@ namespace {
 #endif
 constexpr bool kDigestStagingMapped = DPOW_DIGEST_STAGING_MAPPED != 0;
 constexpr uint32_t kDigestSamples = 16;  // per chunk: the first, the last and 14 evenly spaced entries
-
-// One buffer set: kDigestChunk indices, digests and depth bytes, in pinned mapped memory and (for the
-// "copy" staging, allocated by its first use) in device memory, and the events of its launch.
-constexpr size_t kDigestIdxOff = 0;
-constexpr size_t kDigestOutOff = kDigestIdxOff + (size_t)kDigestChunk * 8;
-constexpr size_t kDigestTzOff = kDigestOutOff + (size_t)kDigestChunk * 16;
-constexpr size_t kDigestSetBytes = kDigestTzOff + kDigestChunk;
-struct DigestSet {
-    char *h_mem = nullptr;    // pinned, mapped
-    char *d_h_mem = nullptr;  // device alias of h_mem
-    char *d_mem = nullptr;    // device ("copy" staging only)
-    hipEvent_t start = nullptr, stop = nullptr;  // around the kernel (timing)
-    hipEvent_t done = nullptr;                   // behind the launch's last copy
-};
 
 }  // namespace
 
@@ -121,6 +108,12 @@ int digest_sets(DigestState &s, bool mapped) {
     return e == hipSuccess ? 0 : hip_fail(e, "dpow_digests: allocation");
 }
 
+}  // namespace
+
+void digests_free(DigestState *s) {
+    if (s) digest_state_free(s);
+}
+
 // DPOW_DIAG_DIGEST_CHUNK: the entries per chunk of this call.
 uint32_t digest_chunk() {
     if (const char *v = getenv("DPOW_DIAG_DIGEST_CHUNK")) {
@@ -145,10 +138,11 @@ uint32_t digest_shape(uint32_t count, uint32_t &group) {
     return (count + group - 1) / group;
 }
 
-}  // namespace
-
-void digests_free(DigestState *s) {
-    if (s) digest_state_free(s);
+int digests_staging(DigestState **state, hipStream_t stream, bool mapped, const char *who, DigestSet **sets) {
+    int rc = digest_state(state, stream, who);
+    if (rc < 0 || (rc = digest_sets(**state, mapped)) < 0) return rc;
+    *sets = (*state)->set;
+    return 0;
 }
 
 int digests_run(DigestState **state, hipStream_t stream, const volatile uint32_t *cancel, const uint8_t *nonce,

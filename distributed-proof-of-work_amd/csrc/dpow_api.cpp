@@ -1,7 +1,7 @@
 // dpow_api.cpp -- the C ABI (include/dpow.h) over the gfx950 search kernels: the context's
 // lifecycle (dpow_open, dpow_close), its accessors and stats, the argument-checking entry points
 // of the searches (dpow_search: search.cpp; dpow_search_batch: batch.cpp; dpow_scan: scan.cpp;
-// dpow_census_window: census.cpp; dpow_census_batch: census_many.cpp; dpow_scan_batch: scan_many.cpp; dpow_digests, dpow_digests_device: digests.cpp; dpow_scan_device: scan_dev.cpp; dpow_scan_batch_device: scan_many_dev.cpp; dpow_search_bound) and the pure host helpers.  The node layer is node.cpp, the dpow_diag_* entry points diag.cpp.
+// dpow_census_window: census.cpp; dpow_census_batch: census_many.cpp; dpow_scan_batch: scan_many.cpp; dpow_digests, dpow_digests_device: digests.cpp; dpow_scan_device: scan_dev.cpp; dpow_scan_batch_device: scan_many_dev.cpp; dpow_digests_batch, dpow_digests_batch_device: digests_many.cpp; dpow_search_bound) and the pure host helpers.  The node layer is node.cpp, the dpow_diag_* entry points diag.cpp.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -17,6 +17,7 @@
 #include "census_many.h"
 #include "ctx.h"
 #include "digests.h"
+#include "digests_many.h"
 #include "md5_host.h"
 #include "md5_variants.h"
 #include "scan.h"
@@ -193,6 +194,7 @@ void dpow_close(dpow_ctx *c) {
     digests_free(c->digests);
     scan_dev_free(c->scan_dev);
     scan_many_dev_free(c->scan_many_dev);
+    digests_many_free(c->digests_many);
     if (c->d_ctrl_alloc) (void)hipFree(c->d_ctrl_alloc);
     if (c->d_claims) (void)hipFree(c->d_claims);
     if (c->h_snap) (void)hipHostFree(c->h_snap);
@@ -464,6 +466,43 @@ int dpow_digests_device(dpow_ctx *c, const uint8_t *nonce, size_t nonce_len, con
     if (on_device.e != hipSuccess) return hip_fail(on_device.e, "hipSetDevice");
     c->last_use.store(now_ns(), std::memory_order_relaxed);
     return digests_run_device(&c->digests, c->stream, nonce, nonce_len, d_global_idx, n, d_digest_out, d_tz_out, stats);
+}
+
+int dpow_digests_batch(dpow_ctx *c, dpow_digest_task *tasks, size_t n_tasks, const uint64_t *rows,
+                       const uint64_t *global_idx, uint8_t *digest_out, uint8_t *tz_out, size_t *n_done,
+                       dpow_batch_stats *stats) {
+    const int rc = digests_many_check(tasks, n_tasks, rows, global_idx, n_done);  // the call's own errors first: they need no context
+    if (rc < 0) return rc;
+    if (!c) return set_error(DPOW_EINVAL, "dpow_digests_batch: ctx is NULL");
+    if (c->node) return set_error(DPOW_EINVAL, "dpow_digests_batch: a node slot is attached to the context");
+    for (size_t i = 0; i < n_tasks; ++i) {
+        tasks[i].n_entries = rows[i + 1] - rows[i];
+        tasks[i].n_shallow = 0;
+    }
+    *n_done = 0;
+    if (stats) *stats = dpow_batch_stats{};
+    if (rows[n_tasks] == 0) return DPOW_EXHAUSTED;
+    if (__atomic_load_n(c->h_cancel, __ATOMIC_ACQUIRE) != 0u) return DPOW_CANCELLED;  // raised on entry: no launch
+    const DeviceScope on_device(c->device);
+    if (on_device.e != hipSuccess) return hip_fail(on_device.e, "hipSetDevice");
+    c->last_use.store(now_ns(), std::memory_order_relaxed);
+    return digests_many_run(&c->digests_many, &c->digests, c->stream, c->h_cancel, tasks, n_tasks, rows, global_idx,
+                            digest_out, tz_out, n_done, stats);
+}
+
+int dpow_digests_batch_device(dpow_ctx *c, dpow_digest_task *tasks, size_t n_tasks, const void *d_rows,
+                              const void *d_global_idx, size_t n, void *d_digest_out, void *d_tz_out,
+                              dpow_batch_stats *stats) {
+    const int rc = digests_many_check_device(tasks, n_tasks, d_rows, d_global_idx, d_digest_out);  // the call's own errors first: they need no context
+    if (rc < 0) return rc;
+    if (!c) return set_error(DPOW_EINVAL, "dpow_digests_batch_device: ctx is NULL");
+    if (c->node) return set_error(DPOW_EINVAL, "dpow_digests_batch_device: a node slot is attached to the context");
+    if (stats) *stats = dpow_batch_stats{};
+    const DeviceScope on_device(c->device);
+    if (on_device.e != hipSuccess) return hip_fail(on_device.e, "hipSetDevice");
+    c->last_use.store(now_ns(), std::memory_order_relaxed);
+    return digests_many_run_device(&c->digests_many, c->stream, tasks, n_tasks, d_rows, d_global_idx, n, d_digest_out,
+                                   d_tz_out, stats);
 }
 
 int dpow_search(dpow_ctx *c, const uint8_t *nonce, size_t nonce_len, uint32_t ntz, uint32_t worker_byte,

@@ -35,6 +35,10 @@
 //   dpow_cli digest <nonce-hex> <idx> [idx ...] [--device N]
 //       the MD5 and the depth of the listed global indices (dpow_digests), one line per entry: its
 //       index, its depth, its secret in hex and its md5 in hex
+//   dpow_cli digest-many <ntz> <nonce-hex>:<idx>[,<idx>...] [<nonce-hex>:<idx>,... ...] [--device N]
+//       the same for lists of many nonces in one call (dpow_digests_batch; a nonce with nothing behind
+//       its colon is an empty task): `digest`'s line per entry, and per task a line "# <nonce-hex>
+//       <entries> <shallow>", shallow being its entries with a depth below ntz
 //   dpow_cli digest-host <nonce-hex> <log2-n> [reps]
 //       time dpow_digest_of_index in a loop over 2^n sequential indices from 2^32 (no GPU): what a
 //       caller pays per entry on the host; one JSON line with the median of `reps` loops
@@ -633,6 +637,64 @@ static int cmd_digest(int argc, char **argv) {
     return rc == DPOW_EXHAUSTED ? 0 : 1;
 }
 
+static int cmd_digest_many(int argc, char **argv) {
+    if (argc < 4) return 2;
+    const uint32_t ntz = (uint32_t)atoi(argv[2]);
+    int dev = 0;
+    std::vector<std::vector<uint8_t>> nonces;
+    std::vector<uint64_t> rows{0}, idx;
+    for (int i = 3; i < argc; ++i) {
+        if (!strcmp(argv[i], "--device") && i + 1 < argc) {
+            dev = atoi(argv[++i]);
+            continue;
+        }
+        const char *colon = strchr(argv[i], ':');
+        if (!colon) return 2;
+        nonces.push_back(from_hex(std::string(argv[i], (size_t)(colon - argv[i])).c_str()));
+        for (const char *q = colon + 1; *q;) {
+            char *end = nullptr;
+            idx.push_back(strtoull(q, &end, 0));
+            if (end == q) return 2;
+            q = *end == ',' ? end + 1 : end;
+        }
+        rows.push_back(idx.size());
+    }
+    if (nonces.empty()) return 2;
+    std::vector<dpow_digest_task> tasks(nonces.size());
+    for (size_t t = 0; t < tasks.size(); ++t) {
+        tasks[t] = dpow_digest_task{};
+        tasks[t].nonce = nonces[t].data();
+        tasks[t].nonce_len = nonces[t].size();
+        tasks[t].ntz = ntz;
+    }
+    dpow_ctx *ctx = nullptr;
+    int rc = dpow_open(dev, &ctx);
+    if (rc) return fail("dpow_open", rc);
+    std::vector<uint8_t> digest(16 * idx.size() + 16), tz(idx.size() + 1);
+    idx.push_back(0);  // (never read: an empty list still has an address)
+    size_t n_done = 0;
+    rc = dpow_digests_batch(ctx, tasks.data(), tasks.size(), rows.data(), idx.data(), digest.data(), tz.data(), &n_done,
+                            nullptr);
+    if (rc < 0) return fail("dpow_digests_batch", rc);
+    for (size_t t = 0; t < tasks.size(); ++t) {
+        printf("# ");
+        for (uint8_t b : nonces[t]) printf("%02x", b);
+        printf(" %llu %llu\n", (unsigned long long)tasks[t].n_entries, (unsigned long long)tasks[t].n_shallow);
+        for (size_t i = rows[t]; i < rows[t + 1] && i < n_done; ++i) {
+            uint8_t sec[DPOW_MAX_SECRET];
+            size_t len = 0;
+            dpow_secret_from_index(idx[i], sec, &len);
+            printf("%llu %u ", (unsigned long long)idx[i], tz[i]);
+            for (size_t b = 0; b < len; ++b) printf("%02x", sec[b]);
+            printf(" ");
+            for (size_t b = 0; b < 16; ++b) printf("%02x", digest[16 * i + b]);
+            printf("\n");
+        }
+    }
+    dpow_close(ctx);
+    return rc == DPOW_EXHAUSTED ? 0 : 1;
+}
+
 static int cmd_digest_host(int argc, char **argv) {
     if (argc < 4) return 2;
     std::vector<uint8_t> nonce = from_hex(argv[2]);
@@ -661,6 +723,7 @@ static int cmd_digest_host(int argc, char **argv) {
 
 int main(int argc, char **argv) {
     if (argc >= 2 && !strcmp(argv[1], "digest")) return cmd_digest(argc, argv);
+    if (argc >= 2 && !strcmp(argv[1], "digest-many")) return cmd_digest_many(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "digest-host")) return cmd_digest_host(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "census")) return cmd_census(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "census-many")) return cmd_census_many(argc, argv);
@@ -686,6 +749,7 @@ int main(int argc, char **argv) {
             "       dpow_cli census <nonce-hex> <k_begin> <k_end> [worker_byte worker_bits [device]]\n"
             "       dpow_cli census-many <k_begin> <k_end> <nonce-hex> [<nonce-hex> ...] [--device N]\n"
             "       dpow_cli digest <nonce-hex> <idx> [idx ...] [--device N]\n"
+            "       dpow_cli digest-many <ntz> <nonce-hex>:<idx>[,<idx>...] [...] [--device N]\n"
             "       dpow_cli digest-host <nonce-hex> <log2-n> [reps]\n");
     return 2;
 }

@@ -135,6 +135,18 @@ class ScanTaskC(ctypes.Structure):
                 ("status", ctypes.c_int32), ("first_hit", ctypes.c_uint64), ("n_hits", ctypes.c_uint64)]
 
 
+class DigestTaskC(ctypes.Structure):
+    """dpow_digest_task (include/dpow.h)."""
+    _fields_ = [("nonce", ctypes.c_void_p), ("nonce_len", ctypes.c_size_t), ("ntz", ctypes.c_uint32),
+                ("n_entries", ctypes.c_uint64), ("n_shallow", ctypes.c_uint64)]
+
+
+class DigestPassC(ctypes.Structure):
+    """dpow_digest_pass (include/dpow.h)."""
+    _fields_ = [("lo", ctypes.c_uint64), ("hi", ctypes.c_uint64), ("task", ctypes.c_uint32),
+                ("pad", ctypes.c_uint32)]
+
+
 SCAN_MANY_MAX_BLOCKS = 20480  # descriptors of one launch (csrc/md5_scan_many.h kScanManyMaxBlocks)
 
 
@@ -345,6 +357,12 @@ def lib():
         "dpow_digests_device": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_size_t, vp, ctypes.c_size_t, vp, vp,
                                                ctypes.POINTER(BatchStats)]),
         "dpow_digest_of_index": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint64, u8p, u32p]),
+        "dpow_digests_batch": (ctypes.c_int, [vp, ctypes.POINTER(DigestTaskC), ctypes.c_size_t, vp, vp, vp, vp, szp,
+                                              ctypes.POINTER(BatchStats)]),
+        "dpow_digests_batch_device": (ctypes.c_int, [vp, ctypes.POINTER(DigestTaskC), ctypes.c_size_t, vp, vp,
+                                                     ctypes.c_size_t, vp, vp, ctypes.POINTER(BatchStats)]),
+        "dpow_digests_batch_walk": (ctypes.c_int, [u64p, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint64,
+                                                   ctypes.POINTER(DigestPassC), ctypes.c_size_t]),
         "dpow_queue_open": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(vp)]),
         "dpow_queue_close": (None, [vp]),
         "dpow_queue_submit": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32,

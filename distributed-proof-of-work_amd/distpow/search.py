@@ -196,6 +196,17 @@ def scan_device_cut(inclusive_prefix: Sequence[int], room: int) -> int:
     return lib().dpow_scan_device_cut(arr, n, room)
 
 
+def digests_batch_walk(rows: Sequence[int], e_first: int, e_end: int):
+    """The passes [(task, lo, hi), ...] of one wave of the digests of many nonces over the list
+    positions [e_first, e_end) (dpow_digests_batch_walk, the walk digest_many_kernel makes): `rows`
+    holds the n_tasks + 1 row pointers, whatever they are."""
+    n = len(rows) - 1
+    arr = (ctypes.c_uint64 * (n + 1))(*rows)
+    out = (_lib.DigestPassC * max(n, 1))()
+    cnt = check(lib().dpow_digests_batch_walk(arr, n, e_first, e_end, out, n), "dpow_digests_batch_walk")
+    return [(p.task, p.lo, p.hi) for p in out[:min(cnt, n)]]
+
+
 def scan_batch_device_settle(blocks, n_fit: int, i_begin: Sequence[int], i_end: Sequence[int], i_done: Sequence[int],
                              next_row: int = 0, unfinished: int = _lib.MORE):
     """What the first `n_fit` workgroup descriptors of a launch having been placed means for the tasks
@@ -229,6 +240,20 @@ class ScanTask:
     worker_bits: int = 0
     k_begin: int = 0
     k_end: int = 1
+
+
+_DIGEST_TASK_IN = struct.Struct("@PNI")  # dpow_digest_task: the input fields
+_DIGEST_TASK = struct.Struct("@PNIQQ")
+assert _DIGEST_TASK.size == ctypes.sizeof(_lib.DigestTaskC) and _lib.DigestTaskC.n_entries.offset == 24
+
+
+@dataclass
+class DigestTask:
+    """One task of Miner.digests_many: the arguments of Miner.digests (dpow_digest_task), and the depth
+    its entries are held against (0: none)."""
+    nonce: Sequence[int]
+    indices: Sequence[int]
+    num_trailing_zeros: int = 0
 
 
 def scan_plan(windows, cap: int = 0, capacity: int = 0):
@@ -746,6 +771,128 @@ class Miner:
         if not (r == _lib.ERANGE and not strict):
             check(r, "dpow_digests_device")
         return dig, dep
+
+    # -- digests of many nonces -------------------------------------------------
+    @staticmethod
+    def _digest_tasks(tasks):
+        """(array, keep-alive) of dpow_digest_task for anything with .nonce and .num_trailing_zeros."""
+        n = len(tasks)
+        arr = (_lib.DigestTaskC * max(n, 1))()
+        nonces = [_b(t.nonce) for t in tasks]
+        buf = ctypes.create_string_buffer(b"".join(nonces), max(sum(map(len, nonces)), 1))  # alive for the call
+        addr = ctypes.addressof(buf)
+        raw = (ctypes.c_ubyte * ctypes.sizeof(arr)).from_buffer(arr)
+        for j, (t, nb) in enumerate(zip(tasks, nonces)):
+            _DIGEST_TASK_IN.pack_into(raw, j * _DIGEST_TASK.size, addr, len(nb), t.num_trailing_zeros)
+            addr += len(nb)
+        return arr, buf
+
+    @staticmethod
+    def _digest_task_outs(arr, n):
+        """([n_entries], [n_shallow]) of the first n task structs."""
+        fields = list(_DIGEST_TASK.iter_unpack(ctypes.string_at(arr, n * _DIGEST_TASK.size)))
+        return [f[3] for f in fields], [f[4] for f in fields]
+
+    _DIGESTS_MANY_KEEP = 1 << 21  # entries: 50 MB of buffers at the most stay with the Miner
+
+    def _digests_many_buffers(self, n):
+        """(indices, digests, depths) for a dpow_digests_batch call of n entries.  Lists of up to
+        _DIGESTS_MANY_KEEP entries reuse buffers kept with the Miner: the first touch of fresh pages
+        cost a call of 2^20 entries more than its GPU work.  (The outputs are copied out per task.)"""
+        kept = getattr(self, "_digests_many_kept", None)
+        if kept is not None and kept[0] >= n:
+            return kept[1:]
+        cap = max(n, 1)
+        made = (cap, (ctypes.c_uint64 * cap)(), ctypes.create_string_buffer(16 * cap), ctypes.create_string_buffer(cap))
+        if cap <= self._DIGESTS_MANY_KEEP:
+            self._digests_many_kept = made
+        return made[1:]
+
+    def digests_many(self, tasks: Sequence[DigestTask], want_digests: bool = True, want_depths: bool = True):
+        """[(digests, depths), ...], one per task, each what Miner.digests returns for the task's nonce
+        and indices (dpow_digests_batch: every task's list in one pass, more than DPOW_BATCH_MAX tasks
+        split across calls).  With neither output wanted the call is a pure check.
+        last_digest_many_shallow[i] is the number of task i's entries with a depth below its
+        num_trailing_zeros, last_digest_many_stats the sums over the calls, last_digest_many_status the
+        last call's status: a raised cancel flag ends it early (CANCELLED) with shorter or empty
+        outputs for the tasks not done."""
+        out, shallow, total = [], [], _lib.BatchStats()
+        status = EXHAUSTED
+        for at in range(0, len(tasks), _lib.DPOW_BATCH_MAX):
+            part = tasks[at:at + _lib.DPOW_BATCH_MAX]
+            if status != EXHAUSTED:  # cancelled: the tasks behind are not begun
+                out += [(b"" if want_digests else None, b"" if want_depths else None) for _ in part]
+                shallow += [0] * len(part)
+                continue
+            arr, keep = self._digest_tasks(part)
+            lists = [self._u64_list(t.indices) for t in part]
+            rows = (ctypes.c_uint64 * (len(part) + 1))()
+            for j, (_, _, cnt) in enumerate(lists):
+                rows[j + 1] = rows[j] + cnt
+            n = rows[len(part)]
+            idx, dig, dep = self._digests_many_buffers(n)
+            for j, (_, addr, cnt) in enumerate(lists):
+                if cnt:
+                    ctypes.memmove(ctypes.addressof(idx) + 8 * rows[j], addr, 8 * cnt)
+            dig, dep = dig if want_digests else None, dep if want_depths else None
+            done, st = ctypes.c_size_t(), _lib.BatchStats()
+            status = check(lib().dpow_digests_batch(self._ctx, arr, len(part), rows, idx, dig, dep, ctypes.byref(done),
+                                                    ctypes.byref(st)), "dpow_digests_batch")
+            del keep, lists
+            total.launches += st.launches
+            total.rounds += st.rounds
+            total.candidates += st.candidates
+            total.kernel_ms += st.kernel_ms
+            m = done.value
+            shallow += self._digest_task_outs(arr, len(part))[1]
+            for j in range(len(part)):
+                lo, hi = min(rows[j], m), min(rows[j + 1], m)
+                out.append((ctypes.string_at(ctypes.addressof(dig) + 16 * lo, 16 * (hi - lo)) if want_digests else None,
+                            ctypes.string_at(ctypes.addressof(dep) + lo, hi - lo) if want_depths else None))
+        self.last_digest_many_shallow, self.last_digest_many_stats, self.last_digest_many_status = shallow, total, status
+        return out
+
+    def digests_many_cuda(self, tasks, idx, rows, want_digests: bool = True, want_depths: bool = True,
+                          strict: bool = True):
+        """(digests [n, 16], depths [n], shallow) of a CSR list on this context's device
+        (dpow_digests_batch_device): `idx` is a CUDA torch.int64 tensor of n global indices and `rows` one
+        of len(tasks) + 1 row pointers, entry e with rows[i] <= e < rows[i + 1] being a candidate of
+        tasks[i].nonce -- what scan_many_cuda returns; `tasks` is any sequence with .nonce and
+        .num_trailing_zeros, so scan_many_cuda's own ScanTask list passes straight through.  The
+        outputs are uint8 tensors on the same device (None where not wanted), nothing crossing to the
+        host but len(tasks) + 1 rows and `shallow`, the per-task counts of entries with a depth below
+        the task's num_trailing_zeros.  An entry beyond DPOW_K_LIMIT reads depth 255 and a zero digest,
+        and the call raises DpowError with code ERANGE -- or, with strict=False, returns the outputs so
+        marked; an entry no row covers reads the same and always raises (EINVAL).  torch's current
+        stream is synchronised before the call, and the outputs are complete on return."""
+        import torch
+        for name, t in (("idx", idx), ("rows", rows)):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int64 and t.dim() == 1):
+                raise ValueError(f"digests_many_cuda: {name} must be a one-dimensional CUDA torch.int64 tensor")
+            if t.device.index != self.device:
+                raise ValueError(f"digests_many_cuda: {name} is on {t.device}, the context on device {self.device}")
+        if rows.numel() != len(tasks) + 1:
+            raise ValueError("digests_many_cuda: rows must hold len(tasks) + 1 row pointers")
+        if len(tasks) > _lib.DPOW_BATCH_MAX:
+            raise ValueError("digests_many_cuda: more than DPOW_BATCH_MAX tasks")
+        idx, rows = idx.contiguous(), rows.contiguous()
+        n = idx.numel()
+        dig = torch.empty((n, 16), dtype=torch.uint8, device=idx.device) if want_digests else None
+        dep = torch.empty((n,), dtype=torch.uint8, device=idx.device) if want_depths else None
+        arr, keep = self._digest_tasks(tasks)
+        st = _lib.BatchStats()
+        pad = idx if n else rows  # (an empty list still goes through the call's argument checks)
+        torch.cuda.current_stream(idx.device).synchronize()
+        r = lib().dpow_digests_batch_device(self._ctx, arr, len(tasks), rows.data_ptr(), pad.data_ptr(), n,
+                                            dig.data_ptr() if want_digests and n else None,
+                                            dep.data_ptr() if want_depths and n else None, ctypes.byref(st))
+        del keep
+        self.last_digest_many_stats, self.last_digest_many_status = st, r
+        self.last_digest_many_entries, shallow = self._digest_task_outs(arr, len(tasks))
+        self.last_digest_many_shallow = shallow
+        if not (r == _lib.ERANGE and not strict):
+            check(r, "dpow_digests_batch_device")
+        return dig, dep, shallow
 
     # -- device scan ------------------------------------------------------------
     def scan_cuda_page(self, nonce: Sequence[int], num_trailing_zeros: int, worker_byte: int = 0,

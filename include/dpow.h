@@ -40,7 +40,8 @@ extern "C" {
  * dpow_digest_of_index) and the batched census (dpow_census_batch, dpow_census_plan) and the
  * batched scan (dpow_scan_batch, dpow_scan_plan, dpow_scan_plan_halve) and the device scan
  * (dpow_scan_device, dpow_scan_device_cut, DPOW_SCAN_DEVICE_MIN_HITS) and the batched device
- * scan (dpow_scan_batch_device, dpow_scan_batch_device_settle).
+ * scan (dpow_scan_batch_device, dpow_scan_batch_device_settle) and the digests of many nonces
+ * (dpow_digests_batch, dpow_digests_batch_device, dpow_digests_batch_walk).
  * A consumer built against another version must refuse the library before any
  * other call (distpow/_lib.py check_abi, tests/c/abi_harness.c). */
 #define DPOW_ABI_VERSION 5
@@ -510,6 +511,61 @@ int dpow_digest_of_index(const uint8_t *nonce, size_t nonce_len, uint64_t global
                          uint8_t digest_out[16], uint32_t *tz_out);   /* pure host */
 
 /* ---------------------------------------------------------------------------
+ * Digests of many nonces (added within ABI 5): dpow_digests for a list that mixes nonces.
+ *
+ * The list is in CSR order, as dpow_scan_batch_device leaves its hits: entry e with
+ * rows[i] <= e < rows[i + 1] is a global index of tasks[i].nonce, and its outputs are exactly what
+ * dpow_digests writes for (tasks[i].nonce, global_idx[e]), 16 bytes and a depth byte at position
+ * e.  Empty tasks are legal anywhere.  Both outputs may be NULL, unlike dpow_digests: the call is
+ * then a pure check that moves 8 bytes per entry in and returns, per task, n_shallow -- how many of
+ * its entries done by the call have a depth below the task's ntz (0: none can).  One generic kernel
+ * (csrc/md5_digest_many.hip) finds each entry's task on the device; DESIGN.md section 21.
+ *
+ * dpow_digests_batch returns, before any GPU work, DPOW_EINVAL for a NULL tasks, rows, global_idx
+ * or n_done, n_tasks of 0 or above DPOW_BATCH_MAX, a NULL nonce with a non-zero nonce_len, a nonce
+ * longer than DPOW_MAX_NONCE, rows[0] != 0 or a descending row, DPOW_ERANGE for an entry with
+ * (g >> 8) >= DPOW_K_LIMIT -- these need no context -- and DPOW_EINVAL for a NULL ctx or a context
+ * with a node slot attached; nothing is written then.  Otherwise it sets every n_entries, and works
+ * the list in dpow_digests' chunks and staging (DPOW_DIAG_DIGEST_CHUNK, DPOW_DIAG_DIGEST_STAGING).
+ * The cancel flag is checked on entry and between chunks: DPOW_CANCELLED with *n_done entries
+ * complete and n_shallow covering those; DPOW_EXHAUSTED with *n_done = rows[n_tasks] otherwise.  Per
+ * chunk the host recomputes 16 samples, each with its own task's nonce, and compares every output
+ * asked for; a mismatch is DPOW_EVERIFY.
+ *
+ * dpow_digests_batch_device is the same kernel on lists already in device memory: d_rows holds
+ * n_tasks + 1 uint64 (8-byte aligned), which the host does not read before the launches; n is the
+ * caller's count of entries in d_global_idx (8-byte aligned), d_digest_out (16-byte aligned) and
+ * d_tz_out, either or both of which may be NULL.  It makes one bounded launch per 2^24 entries
+ * and drains the stream once; behind the last launch it copies out the rows (n_entries), the
+ * shallow counts and two count words.  An entry outside [rows[0], rows[n_tasks]) gets the depth
+ * byte 0xFF and a zero digest, and the call returns DPOW_EINVAL; an entry beyond DPOW_K_LIMIT
+ * likewise, and the call returns DPOW_ERANGE; the other entries are written all the same.  It
+ * verifies nothing on the host and does not look at the cancel flag.  Rows that descend cost wrong
+ * outputs, never an access outside the arrays as described.  DPOW_EINVAL up front for a NULL
+ * tasks, d_rows or d_global_idx, a misaligned pointer, a bad n_tasks or nonce, a NULL ctx or an
+ * attached node slot.
+ *
+ * One search, batch, scan, census or digest call is in flight per context.
+ * ------------------------------------------------------------------------- */
+typedef struct dpow_digest_task {
+    const uint8_t *nonce; size_t nonce_len;   /* in */
+    uint32_t ntz;                             /* in: the depth this task's entries are held against (0: none) */
+    uint64_t n_entries;                       /* out: rows[i + 1] - rows[i] */
+    uint64_t n_shallow;                       /* out: entries of the task done by this call with depth < ntz */
+} dpow_digest_task;
+
+int dpow_digests_batch(dpow_ctx *ctx, dpow_digest_task *tasks, size_t n_tasks,
+                       const uint64_t *rows /* n_tasks + 1 */, const uint64_t *global_idx /* rows[n_tasks] */,
+                       uint8_t *digest_out /* 16 per entry, may be NULL */, uint8_t *tz_out /* may be NULL */,
+                       size_t *n_done, dpow_batch_stats *stats /* may be NULL */);
+int dpow_digests_batch_device(dpow_ctx *ctx, dpow_digest_task *tasks, size_t n_tasks,
+                              const void *d_rows /* n_tasks + 1 uint64 in device memory */,
+                              const void *d_global_idx, size_t n,
+                              void *d_digest_out, void *d_tz_out,
+                              dpow_batch_stats *stats /* may be NULL */);
+/* (dpow_digests_batch_walk, a wave's passes over the rows, is with the host helpers below.) */
+
+/* ---------------------------------------------------------------------------
  * Task queue (added within ABI 5): the batched search as a service on one GPU.
  *
  * dpow_search_batch wants its tasks at once and returns when the slowest is decided; the
@@ -853,6 +909,24 @@ void dpow_scan_plan_halve(uint64_t total, uint64_t weight, uint64_t *cap_out, ui
  * hits fit: n_groups when the slice's total fits, 0 when not even the first does (or for a NULL
  * prefix). */
 size_t dpow_scan_device_cut(const uint32_t *inclusive_prefix, size_t n_groups, size_t room);
+
+/* The passes of one wave of the digests of many nonces (device logic of csrc/md5_digest_many.hip,
+ * the same code compiled for the host, exposed for testing): the wave holds
+ * the list positions [e_first, e_end), at most 64, and makes one pass per task whose segment
+ * [rows[t], rows[t + 1]) meets them in a non-empty [lo, hi), in ascending task order.  Returns the
+ * number of passes and writes the first max_passes of them.  Whatever the rows hold it reads
+ * rows[0 .. n_tasks] only, makes at most n_tasks passes, and every pass has task < n_tasks and
+ * e_first <= lo < hi <= e_end; with rows that do not descend the passes are disjoint and cover
+ * exactly the wave's positions within [rows[0], rows[n_tasks]).  DPOW_EINVAL for a NULL rows (or
+ * out with max_passes > 0), n_tasks of 0 or above DPOW_BATCH_MAX, e_end < e_first or more than 64
+ * positions. */
+typedef struct dpow_digest_pass {
+    uint64_t lo, hi;
+    uint32_t task;
+    uint32_t pad_;
+} dpow_digest_pass;
+int dpow_digests_batch_walk(const uint64_t *rows, size_t n_tasks, uint64_t e_first, uint64_t e_end,
+                            dpow_digest_pass *out, size_t max_passes);
 
 /* What a launch means for the tasks (host logic of dpow_scan_batch_device, exposed for testing;
  * DESIGN.md section 20): the first n_fit workgroup descriptors of a launch (entries of

@@ -50,6 +50,10 @@
 #                    scan_many_kernel's, its calls beside Miner.scan_many's and Miner.scan_cuda's in a loop and
 #                    the call's host time against hits and tasks (tools/scan_many_device_rate.py ->
 #                    scan_many_device_rate.json)
+#   digest-many [reps]   the GPU tests of the digests of many nonces, then the kernel beside digest_kernel on
+#                    one task, one call beside the looped digests_cuda, the worst case beside the host loop, the
+#                    chain behind the batched device scan, the host form and the call's host time
+#                    (tools/digest_many_rate.py -> digest_many_rate.json)
 set -o pipefail
 task=${1:?task}; tag=${2:?tag}; shift 2
 out=gpurun_out/$tag
@@ -167,6 +171,10 @@ scan-many-device)
     timeout -k 10 300 python3 -u -m pytest tests/test_gpu_scan_many_dev.py -m gpu -x -v -s > $out/pytest_scan_many_dev.txt 2>&1 &&
     timeout -k 10 500 python3 -u tools/scan_many_device_rate.py --reps "${1:-5}" --out $out/scan_many_device_rate.json \
         > $out/scan_many_device_rate.txt 2> $out/scan_many_device_rate.err ;;
+digest-many)
+    timeout -k 10 300 python3 -u -m pytest tests/test_gpu_digests_many.py -m gpu -x -v -s > $out/pytest_digests_many.txt 2>&1 &&
+    timeout -k 10 500 python3 -u tools/digest_many_rate.py --reps "${1:-5}" --out $out/digest_many_rate.json \
+        > $out/digest_many_rate.txt 2> $out/digest_many_rate.err ;;
 ab) timeout -k 10 800 python3 -u tools/ab_variants.py "$@" > $out/ab.log 2>&1 ;;
 node-ab)
     runs=$1; shift

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Device-only disassembly of every kernel translation unit of libdpow.so (the 8 (NBLK, SH) units,
-# the 2 chunk-length-spanning units, the segment-inner unit, search_ctrl.hip, the batch, the scan, the census, the batched census, the batched scan, the digest, the device scan and the batched device scan unit), one .s per unit, into DIR: a refactor of
+# the 2 chunk-length-spanning units, the segment-inner unit, search_ctrl.hip, the batch, the scan, the census, the batched census, the batched scan, the digest, the device scan, the batched device scan and the digests-of-many unit), one .s per unit, into DIR: a refactor of
 # the kernel sources that claims to change nothing is checked by diffing two dumps.
 #   bash tools/isa_dump.sh DIR [extra hipcc flags]
 set -e
@@ -32,4 +32,5 @@ unit scan_many md5_scan_many.hip "$@" &  # scan_many_kernel
 unit digest md5_digest.hip "$@" &  # digest_kernel
 unit scan_dev md5_scan_dev.hip "$@" &  # scan_mask_kernel, scan_place_kernel, scan_check_kernel
 unit scan_many_dev md5_scan_many_dev.hip "$@" &  # scan_many_mask_kernel, scan_many_place_kernel, scan_many_rows_kernel, scan_many_depth_kernel
+unit digest_many md5_digest_many.hip "$@" &  # digest_many_kernel
 wait
