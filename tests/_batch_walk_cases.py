@@ -4,11 +4,13 @@ claim, from hashlib, the C oracle and the round planner alone) and tests/test_gp
 The depth reference and families F and G at the end serve the scan and census kernels as well
 (tests/test_listing_walk_cases.py on the CPU, tests/test_gpu_listing_walk.py on the GPU), and the
 device scan (tests/test_gpu_scan_dev_walk.py), whose geometry is restated behind them with family H,
-the windows that reach every group size of it.
+the windows that reach every group size of it, and the batched device scan
+(tests/test_gpu_scan_many_dev_walk.py) with families M and X, the calls of many tasks that reach every
+group size and every prefix round of it (tests/test_scan_many_dev_walk_cases.py on the CPU).
 
 Every expected value here comes from hashlib, the oracle or a committed fixture; nothing calls
-search_batch or search to learn an answer (family H alone holds no hashes: its windows are too long
-for hashlib, and window_depths_cuda takes their depths from the digest kernel).  The builders are
+search_batch or search to learn an answer (families H, M and X hold no hashes: their windows are too
+long for hashlib, and window_depths_cuda takes their depths from the digest kernel).  The builders are
 deterministic (SEED) and cached, so a process computes each family once.
 
 Notation: edge(a) = 256**a is the first k whose chunk is a + 1 bytes long; R = 256 >> worker_bits
@@ -610,6 +612,114 @@ def second_slice_window():
     4097 groups of 512, the last of 352 indices (group, n_blocks and s are the second slice's)."""
     rnd = random.Random(H_SEED + 1)
     return _scan_window("two-slices", rnd, _nonce(rnd, 4), H_WB, H_WBITS, (1 << 28) + (1 << 21) + 352, 512, 4097, 1)
+
+
+# ---- families M and X: the batched device scan, many tasks to a launch ------------------------------
+# No hashes, like family H: tests/test_gpu_scan_many_dev_walk.py takes the lists from the digest kernel,
+# Miner.scan_cuda and Miner.scan_many; tests/test_scan_many_dev_walk_cases.py shows through
+# distpow.census_plan, the unit's planner, that the calls are what they name.  A call's launch holds all
+# its tasks, and its descriptors are cut from each task's begin in pieces of the launch's group,
+# scan_dev_geometry(the launch's total)[0].
+M_SEED = SEED + 41   # (change the offset, not a threshold, if the walk's conditions fail: F_SEED's note)
+X_SEED = SEED + 42
+SCAN_MANY_MAX_BLOCKS = 20480      # csrc/md5_scan_many.h kScanManyMaxBlocks: ten rounds of the prefix
+X_TASKS = 4096                    # DPOW_BATCH_MAX
+X_LARGE_AT = 2047                 # the large task's place in family X's array
+
+
+@dataclass(frozen=True)
+class ScanCall:
+    """One call of the batched device scan: its tasks as ScanWindows in array order (an empty task has
+    k_begin == k_end), the group of its one launch and the length of each task's last descriptor."""
+    name: str
+    group: int
+    windows: tuple
+    lasts: tuple         # local indices of each task's last descriptor (0: an empty task)
+
+    @property
+    def total(self):
+        return sum(w.total for w in self.windows)
+
+    @property
+    def n_descriptors(self):
+        return sum(w.n_blocks for w in self.windows)
+
+    def tasks(self, ntz):
+        return [distpow.ScanTask(w.nonce, ntz, w.wb, w.wbits, w.k_begin, w.k_end) for w in self.windows]
+
+
+def _call_window(name, rnd, nonce_len, wb, wbits, total, group):
+    """A task of `total` local indices in a launch of `group`: its ScanWindow (s: the whole steps of its
+    last descriptor before a ragged one) and the length of its last descriptor."""
+    n_blocks = -(-total // group)
+    last = total - (n_blocks - 1) * group if total else 0
+    w = _scan_window(name, rnd, _nonce(rnd, nonce_len), wb, wbits, total, group, n_blocks,
+                     last // SCAN_DEV_STEP if last % SCAN_DEV_STEP else 0)
+    return w, last
+
+
+def _scan_call(name, group, parts):
+    return ScanCall(name, group, tuple(w for w, _ in parts), tuple(last for _, last in parts))
+
+
+@functools.lru_cache(maxsize=None)
+def family_m():
+    """For each group g of H_GROUPS one call "m{g}" of five tasks with their own nonces, 4096 g + 256 s +
+    673 local indices in all (s as family H: 1 for g = 512, else g / 512), so the launch's group is g:
+      t0  worker_bits 3, 4-byte nonce, 1500 g + 256 s + 96 local indices: 1501 descriptors, the last ragged
+          across steps like family H's (waves 0 and 1 run s + 1 steps, wave 1's last half full);
+      t1  empty;
+      t2  worker_bits 3, 55-byte nonce, 96 local indices: one descriptor shorter than a step, waves 2 and
+          3 run none;
+      t3  worker_bits 0, 56-byte nonce (two final blocks), 2000 g + 256: 2001 descriptors, the last one step;
+      t4  worker_bits 8 (R = 1), 63-byte nonce, 596 g + 225: 597 descriptors, the last one step whose
+          wave 3 has 33 lanes.
+    4100 descriptors: three rounds of the prefix.  And three calls at group 256, "b2047", "b2048" and
+    "b2049", of that many descriptors over three tasks -- 1000 descriptors at worker_bits 3 (the last of
+    96), 500 whole ones at worker_bits 0 with a 56-byte nonce, and the rest at worker_bits 8 (the last of
+    225), so the round boundary behind descriptor 2047 lies inside the third task.  Every k_begin is
+    odd, every worker byte non-zero where the partition has one."""
+    rnd = random.Random(M_SEED)
+    out = []
+    for g in H_GROUPS:
+        s = 1 if g == 512 else g // 512
+        out.append(_scan_call(f"m{g}", g, [
+            _call_window(f"m{g}/t0", rnd, 4, rnd.randrange(1, 8), 3, 1500 * g + 256 * s + 96, g),
+            _call_window(f"m{g}/t1", rnd, 9, 0, 0, 0, g),
+            _call_window(f"m{g}/t2", rnd, 55, rnd.randrange(1, 8), 3, 96, g),
+            _call_window(f"m{g}/t3", rnd, 56, 0, 0, 2000 * g + 256, g),
+            _call_window(f"m{g}/t4", rnd, 63, rnd.randrange(1, 256), 8, 596 * g + 225, g)]))
+    for n in (2047, 2048, 2049):
+        out.append(_scan_call(f"b{n}", 256, [
+            _call_window(f"b{n}/t0", rnd, 4, rnd.randrange(1, 8), 3, 999 * 256 + 96, 256),
+            _call_window(f"b{n}/t1", rnd, 56, 0, 0, 500 * 256, 256),
+            _call_window(f"b{n}/t2", rnd, 63, rnd.randrange(1, 256), 8, (n - 1501) * 256 + 225, 256)]))
+    return tuple(out)
+
+
+def family_m_call(name):
+    return next(c for c in family_m() if c.name == name)
+
+
+@functools.lru_cache(maxsize=None)
+def family_x():
+    """The most descriptors a launch can have: one call of 4096 tasks and 2^28 local indices, group 16384.
+    4095 tasks of one k at worker_bits 0 (256 local indices, one short descriptor each) with 4-byte
+    nonces of their own and k_begin = j % 300, and at array position 2047 one task of 2^28 - 4095 * 256
+    local indices at worker_bits 3: 16320 whole descriptors and one of 256.  20416 descriptors, ten
+    rounds of the prefix: small totals in rounds 0 and 9, large ones between, a whole round behind every
+    carry."""
+    rnd = random.Random(X_SEED)
+    base = rnd.randrange(1 << 32)
+    large = SCAN_DEV_SLICE - (X_TASKS - 1) * 256
+    parts = []
+    for j in range(X_TASKS):
+        if j == X_LARGE_AT:
+            parts.append(_call_window("x/large", rnd, 4, H_WB, H_WBITS, large, SCAN_DEV_MAX_GROUP))
+            continue
+        nonce = ((base + j) & 0xFFFFFFFF).to_bytes(4, "little")
+        parts.append((ScanWindow(f"x/{j}", nonce, 0, 0, j % 300, j % 300 + 1, SCAN_DEV_MAX_GROUP, 1, 0), 256))
+    return _scan_call("x", SCAN_DEV_MAX_GROUP, parts)
 
 
 def window_indices_cuda(wb, wbits, k_begin, n, device, first=0):

@@ -3,6 +3,8 @@ test_gpu_scan_many_dev.py: what a launch's placed descriptors mean for the tasks
 statuses, k_done, rows and total from the tasks' hit lists.  The launches come from
 distpow.census_plan, the batched census's planner, which test_census_many_host.py pins on its own;
 nothing here calls the entry point under test."""
+import numpy as np
+
 import distpow
 
 NO_ROW = None
@@ -49,22 +51,29 @@ def settle_model(blocks, n_fit, i_begin, i_end, i_done, next_row, unfinished):
 
 def call_model(tasks, hits, max_hits, cap=0):
     """One dpow_scan_batch_device call over `tasks` (ScanTasks) whose complete hit lists are
-    `hits[i]` (global indices, increasing): (results, rows, segments) -- results[i] = (status,
-    k_done), rows the n + 1 row pointers, segments[i] the global indices the call lists for task i."""
+    `hits[i]` (global indices, increasing: a list, or a numpy array where the lists are long): (results,
+    rows, segments) -- results[i] = (status, k_done), rows the n + 1 row pointers, segments[i] the global
+    indices the call lists for task i, a leading slice of hits[i].  A partition's local index rises with
+    the global one, so a descriptor's hits are found by bisection."""
     n = len(tasks)
     rbits = [distpow.remainder_bits(t.worker_bits) for t in tasks]
     i_begin = [t.k_begin << r for t, r in zip(tasks, rbits)]
     i_end = [t.k_end << r for t, r in zip(tasks, rbits)]
     done = list(i_begin)
 
-    def local(i, g):  # the local index of global index g of task i
-        return ((g >> 8) << rbits[i]) | (g & ((1 << rbits[i]) - 1))
+    def local(i, g):  # the local indices of the global indices g of task i
+        g = np.asarray(g, dtype=np.uint64)
+        return ((g >> np.uint64(8)) << np.uint64(rbits[i])) | (g & np.uint64((1 << rbits[i]) - 1))
 
-    locs = [[local(i, g) for g in hits[i]] for i in range(n)]
+    def below(i, x):  # how many of task i's hits lie below local index x
+        return int(np.searchsorted(locs[i], np.uint64(x), side="left"))
+
+    locs = [local(i, hits[i]) for i in range(n)]
+    assert all(bool((x[1:] > x[:-1]).all()) for x in locs)
     room, cut = max_hits, False
     for blocks in launches_of(windows_of(tasks), cap):
         for task, lo, hi in blocks:
-            c = sum(1 for x in locs[task] if lo <= x < hi)
+            c = below(task, hi) - below(task, lo)
             if c > room:
                 cut = True
                 break
@@ -72,7 +81,7 @@ def call_model(tasks, hits, max_hits, cap=0):
             done[task] = hi
         if cut:
             break
-    segments = [[g for g, x in zip(hits[i], locs[i]) if x < done[i]] for i in range(n)]
+    segments = [hits[i][:below(i, done[i])] for i in range(n)]
     rows = [0]
     for s in segments:
         rows.append(rows[-1] + len(s))
