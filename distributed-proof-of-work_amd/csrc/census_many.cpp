@@ -1,8 +1,9 @@
 // census_many.cpp -- host side of the batched census: dpow_census_batch's launch loop over the
-// batched census kernel (md5_census_many.hip) on the launch engine (batch_engine.h), its planner
-// and the host helper dpow_census_plan.
+// batched census kernel (md5_census_many.hip) on the launch engine (batch_engine.h) and the host
+// helper dpow_census_plan.
 //
-// Launches.  The tasks are worked in array order.  A launch takes tasks from a cursor until it
+// Launches.  The tasks are worked in array order, by the planner the batched loops share
+// (many_plan.h many_next, without a weight budget).  A launch takes tasks from a cursor until it
 // holds kBatchCap local indices; only its last task can be cut, at a multiple of 256 local indices
 // from the task's begin, and goes on in the next launch.  A task's part of a launch is cut into
 // workgroup descriptors of batch_group(the launch's total) local indices, the last one of a task
@@ -17,7 +18,6 @@
 // caller's tasks before the call's last launch has been folded.
 #include "census_many.h"
 
-#include <stdlib.h>
 #include <string.h>
 
 #include <new>
@@ -28,60 +28,15 @@
 #include "batch_engine.h"
 #include "census.h"
 #include "ctx.h"
+#include "many_plan.h"
 #include "md5_census_many.h"
+#include "md5_host.h"
 #include "plan.h"
 #include "queue.h"
 
 namespace dpow {
 
-bool census_many_next(const uint64_t *i_begin, const uint64_t *i_end, size_t n, uint64_t cap, CensusManyCursor &cur,
-                      std::vector<CensusManyPart> &parts, uint32_t &group) {
-    parts.clear();
-    uint64_t used = 0;
-    while (cur.task < n) {
-        const uint64_t lo = i_begin[cur.task] + cur.done, end = i_end[cur.task];
-        if (lo >= end) {  // an empty task, or one just finished
-            cur.task++;
-            cur.done = 0;
-            continue;
-        }
-        const uint64_t left = end - lo, room = cap - used;
-        const uint64_t take = left <= room ? left : room & ~255ull;
-        if (take == 0) break;  // (never of an empty launch: cap >= 256)
-        parts.push_back(CensusManyPart{(uint32_t)cur.task, lo, lo + take});
-        used += take;
-        if (take < left) {
-            cur.done += take;
-            break;
-        }
-        cur.task++;
-        cur.done = 0;
-    }
-    group = batch_group(used);
-    return !parts.empty();
-}
-
-uint64_t census_many_cap() {
-    if (const char *v = getenv("DPOW_DIAG_CENSUS_MANY_CAP")) {
-        const long long c = atoll(v);
-        if (c >= 256 && (uint64_t)c <= kBatchCap) return (uint64_t)c & ~255ull;
-    }
-    return kBatchCap;
-}
-
 namespace {
-
-// The descriptors of one launch, in task order: each part in pieces of `group` local indices.
-template <typename Emit>
-size_t census_many_blocks(const std::vector<CensusManyPart> &parts, uint32_t group, Emit &&emit) {
-    size_t n_blocks = 0;
-    for (const CensusManyPart &p : parts) {
-        const uint32_t rows = (uint32_t)((p.hi - p.lo + group - 1) / group);
-        for (uint64_t lo = p.lo; lo < p.hi; lo += group, ++n_blocks)
-            emit(n_blocks, p.task, lo, p.hi - lo > group ? lo + group : p.hi, rows);
-    }
-    return n_blocks;
-}
 
 // The context's buffers.  Device: the task table in the engine's image area, the control words
 // behind it (batch_engine.h), then the tasks' tables and the copy of the live-slot list and the
@@ -107,6 +62,7 @@ static_assert(kManyBlocksOff % 32 == 0 && kManyOutOff % 8 == 0 && kManyRecOff % 
 constexpr EngineSections kManyAt{kManyDevTablesOff, kManyOutOff, kManyRecOff};
 
 const char *const kWho = "dpow_census_batch";
+const char *const kCapEnv = "DPOW_DIAG_CENSUS_MANY_CAP";  // (many_plan.h many_cap)
 
 }  // namespace
 
@@ -155,17 +111,7 @@ int census_many_check(const dpow_census_task *tasks, size_t n_tasks) {
     if (!tasks) return set_error(DPOW_EINVAL, "dpow_census_batch: tasks is NULL");
     if (n_tasks == 0 || n_tasks > DPOW_BATCH_MAX)
         return set_error(DPOW_EINVAL, "dpow_census_batch: n_tasks must be in [1, DPOW_BATCH_MAX]");
-    for (size_t i = 0; i < n_tasks; ++i) {
-        dpow_batch_task t{};
-        t.nonce = tasks[i].nonce;
-        t.nonce_len = tasks[i].nonce_len;
-        t.worker_byte = tasks[i].worker_byte;
-        t.k_begin = tasks[i].k_begin;
-        t.k_end = tasks[i].k_end;
-        const int rc = batch_check_task(t, kWho);
-        if (rc < 0) return rc;
-    }
-    return 0;
+    return many_check_tasks(tasks, n_tasks, kWho);
 }
 
 int census_many_run(CensusManyState **state, hipStream_t stream, const volatile uint32_t *cancel,
@@ -173,30 +119,21 @@ int census_many_run(CensusManyState **state, hipStream_t stream, const volatile 
     const size_t n = n_tasks;
     dpow_batch_stats st{};
     // A task's progress: the local indices [i_begin, i_done) are folded into its census.
-    std::vector<uint64_t> i_begin(n), i_end(n), i_done(n);
-    std::vector<uint32_t> rbits(n);
-    bool any = false;
-    for (size_t i = 0; i < n; ++i) {
-        rbits[i] = remainder_bits(tasks[i].worker_bits);
-        i_begin[i] = i_done[i] = tasks[i].k_begin << rbits[i];
-        i_end[i] = tasks[i].k_end << rbits[i];
-        any = any || i_begin[i] < i_end[i];
-    }
+    ManyTasks v = many_tasks(tasks, n);
     std::vector<dpow_census> census;  // (filled only when a launch is made)
     const auto write_out = [&](bool cancelled_on_entry) {
         for (size_t i = 0; i < n; ++i) {
             dpow_census_task &t = tasks[i];
             if (census.empty()) census_clear(t.census);
             else t.census = census[i];
-            const bool finished = i_done[i] == i_end[i] && !cancelled_on_entry;  // (an empty task is)
-            t.status = finished ? DPOW_EXHAUSTED : DPOW_CANCELLED;
-            t.k_done = finished ? t.k_end : i_done[i] >> rbits[i];
+            t.status = v.finished(i, cancelled_on_entry) ? DPOW_EXHAUSTED : DPOW_CANCELLED;
+            t.k_done = v.k_done(i);
         }
         if (stats) *stats = st;
         return 0;
     };
     if (__atomic_load_n(cancel, __ATOMIC_ACQUIRE) != 0u) return write_out(true);  // raised on entry: no launch
-    if (!any) return write_out(false);                                             // only empty tasks: no launch
+    if (!v.any) return write_out(false);                                           // only empty tasks: no launch
 
     int rc = census_many_state(state, stream);
     if (rc < 0) return rc;
@@ -204,19 +141,10 @@ int census_many_run(CensusManyState **state, hipStream_t stream, const volatile 
     census.resize(n);
     for (dpow_census &c : census) census_clear(c);
 
-    // The task table: row i is task i's (ntz 0, as census.cpp fills its own); an empty task's row is
-    // never read.
-    BatchTask *const h_rows = reinterpret_cast<BatchTask *>(s.h_mem + kManyRowsOff);
-    for (size_t i = 0; i < n; ++i)
-        if (i_begin[i] < i_end[i])
-            batch_fill_task(h_rows[i], tasks[i].nonce, tasks[i].nonce_len, 0u, tasks[i].worker_byte, tasks[i].worker_bits);
-    BatchTask *const d_tasks = reinterpret_cast<BatchTask *>(s.d_mem);
-    {
-        const hipError_t e = batch_upload(reinterpret_cast<uint32_t *>(d_tasks),
-                                          reinterpret_cast<const uint32_t *>(s.d_h_mem + kManyRowsOff),
-                                          (uint32_t)(n * sizeof(BatchTask) / 4), stream);
-        if (e != hipSuccess) return hip_fail(e, "dpow_census_batch: upload");
-    }
+    // The task table: row i is task i's (ntz 0, as census.cpp fills its own).
+    if ((rc = many_upload_tasks(tasks, v, s, kManyRowsOff, stream, kWho)) < 0) return rc;
+    const BatchTask *const h_rows = reinterpret_cast<const BatchTask *>(s.h_mem + kManyRowsOff);
+    const BatchTask *const d_tasks = reinterpret_cast<const BatchTask *>(s.d_mem);
     BatchEntry *const h_blocks = reinterpret_cast<BatchEntry *>(s.h_mem + kManyBlocksOff);
     uint32_t *const h_slots = reinterpret_cast<uint32_t *>(s.h_mem + kManySlotsOff);
     const unsigned long long *const h_out = reinterpret_cast<const unsigned long long *>(s.h_mem + kManyOutOff);
@@ -238,45 +166,35 @@ int census_many_run(CensusManyState **state, hipStream_t stream, const volatile 
         return e == hipSuccess ? 0 : hip_fail(e, "dpow_census_batch: launch");
     };
 
-    const uint64_t cap = census_many_cap();
-    CensusManyCursor cur;
-    std::vector<CensusManyPart> parts;
+    const ManyBudget budget{many_cap(kCapEnv), 0};
+    ManyCursor cur;
+    std::vector<ManyPart> parts;
     std::vector<uint8_t> msg;
     uint32_t group = 0;
     for (;;) {
         if (__atomic_load_n(cancel, __ATOMIC_ACQUIRE) != 0u) break;  // what is not finished stays DPOW_CANCELLED
-        if (!census_many_next(i_begin.data(), i_end.data(), n, cap, cur, parts, group)) break;
+        if (!many_next(v.i_begin.data(), v.i_end.data(), nullptr, n, budget, cur, parts, group)) break;
         uint64_t total = 0;
         for (size_t q = 0; q < parts.size(); ++q) {
             h_slots[q] = parts[q].task;
             total += parts[q].hi - parts[q].lo;
         }
-        size_t n_blocks = 0;
-        for (const CensusManyPart &p : parts) n_blocks += (size_t)((p.hi - p.lo + group - 1) / group);
-        if (n_blocks == 0 || n_blocks > kCensusManyMaxBlocks)
+        const size_t n_blocks = many_write_blocks(parts, group, h_blocks, kCensusManyMaxBlocks);
+        if (n_blocks == 0)
             return set_error(DPOW_EINVAL, "dpow_census_batch: the launch plan left the descriptor table");  // never expected
-        census_many_blocks(parts, group, [&](size_t b, uint32_t task, uint64_t lo, uint64_t hi, uint32_t) {
-            BatchEntry &e = h_blocks[b];
-            e.i_begin = lo;
-            e.i_end = hi;
-            e.task = task;
-            e.pad_[0] = e.pad_[1] = e.pad_[2] = 0;
-        });
         rc = engine_launch(s, kManyAt, (uint32_t)parts.size(), group, (uint32_t)n_blocks, stream,
                            "dpow_census_batch: stream idle without the launch's completion record", st, issue);
         if (rc < 0) return rc;
         st.candidates += total;
         for (size_t q = 0; q < parts.size(); ++q) {
-            const CensusManyPart &p = parts[q];
+            const ManyPart &p = parts[q];
             const dpow_census_task &t = tasks[p.task];
             const BatchTask &row = h_rows[p.task];
-            msg.resize(t.nonce_len + DPOW_MAX_SECRET);
-            if (t.nonce_len) memcpy(msg.data(), t.nonce, t.nonce_len);
             const unsigned long long *const table = h_out + q * kCensusTableWords;
-            rc = census_fold_launch(kWho, msg.data(), t.nonce_len, row.rbits, row.base_tb, p.lo, p.hi, table,
-                                    table + kCensusDepths, census[p.task]);
+            rc = census_fold_launch(kWho, md5_msg_of_nonce(msg, t.nonce, t.nonce_len), t.nonce_len, row.rbits,
+                                    row.base_tb, p.lo, p.hi, table, table + kCensusDepths, census[p.task]);
             if (rc < 0) return rc;
-            i_done[p.task] = p.hi;
+            v.i_done[p.task] = p.hi;
         }
     }
     return write_out(false);
@@ -304,22 +222,13 @@ extern "C" int dpow_census_plan(const uint64_t *k_begin, const uint64_t *k_end, 
         i_begin[i] = k_begin[i] << rbits;
         i_end[i] = k_end[i] << rbits;
     }
-    CensusManyCursor cur;
-    std::vector<CensusManyPart> parts;
+    const ManyBudget budget{cap, 0};
+    ManyCursor cur;
+    std::vector<ManyPart> parts;
     uint32_t group = 0;
     uint64_t n_out = 0, launch = 0;
-    for (; census_many_next(i_begin.data(), i_end.data(), n_tasks, cap, cur, parts, group); ++launch) {
-        const size_t n_blocks =
-            census_many_blocks(parts, group, [&](size_t b, uint32_t task, uint64_t lo, uint64_t hi, uint32_t rows) {
-                if (!out || n_out + b >= max_entries) return;
-                dpow_batch_range &o = out[n_out + b];
-                o.launch = (uint32_t)launch;
-                o.task = task;
-                o.i_begin = lo;
-                o.i_end = hi;
-                o.group = group;
-                o.rows = rows;
-            });
+    for (; many_next(i_begin.data(), i_end.data(), nullptr, n_tasks, budget, cur, parts, group); ++launch) {
+        const size_t n_blocks = many_append_ranges(parts, group, launch, out, max_entries, n_out);
         if (n_blocks > kCensusManyMaxBlocks)
             return set_error(DPOW_EINVAL, "dpow_census_plan: a launch beyond its descriptor bound");  // never expected
         n_out += n_blocks;

@@ -250,10 +250,9 @@ int digests_many_run(DigestManyState **state, DigestState **sets_state, hipStrea
             const size_t j = (size_t)(count - 1) * q / (kDigestManySamples - 1);
             // The sample's task: the last row at most its position (the empty tasks there are skipped).
             const size_t t = (size_t)(std::upper_bound(rows, rows + n_tasks + 1, (uint64_t)(first + j)) - rows) - 1;
-            msg.resize(tasks[t].nonce_len + DPOW_MAX_SECRET);
-            if (tasks[t].nonce_len) memcpy(msg.data(), tasks[t].nonce, tasks[t].nonce_len);
             uint8_t d[16];
-            const uint32_t tz = md5_depth_of_index(msg.data(), tasks[t].nonce_len, global_idx[first + j], d);
+            const uint32_t tz = md5_depth_of_index(md5_msg_of_nonce(msg, tasks[t].nonce, tasks[t].nonce_len),
+                                                   tasks[t].nonce_len, global_idx[first + j], d);
             if ((digest_out && memcmp(h_digest + 16 * j, d, 16) != 0) || (tz_out && h_tz[j] != tz))
                 return fail(set_error(DPOW_EVERIFY, "dpow_digests_batch: a sampled entry failed host MD5 verification"));
         }

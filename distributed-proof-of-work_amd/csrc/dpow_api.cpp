@@ -1,7 +1,7 @@
 // dpow_api.cpp -- the C ABI (include/dpow.h) over the gfx950 search kernels: the context's
 // lifecycle (dpow_open, dpow_close), its accessors and stats, the argument-checking entry points
 // of the searches (dpow_search: search.cpp; dpow_search_batch: batch.cpp; dpow_scan: scan.cpp;
-// dpow_census_window: census.cpp; dpow_census_batch: census_many.cpp; dpow_scan_batch: scan_many.cpp; dpow_digests, dpow_digests_device: digests.cpp; dpow_scan_device: scan_dev.cpp; dpow_scan_batch_device: scan_many_dev.cpp; dpow_digests_batch, dpow_digests_batch_device: digests_many.cpp; dpow_search_bound) and the pure host helpers.  The node layer is node.cpp, the dpow_diag_* entry points diag.cpp.
+// dpow_census_window: census.cpp; dpow_census_batch: census_many.cpp; dpow_scan_batch: scan_many.cpp; dpow_digests, dpow_digests_device: digests.cpp; dpow_scan_device: scan_dev.cpp; dpow_scan_batch_device: scan_many_dev.cpp; dpow_digests_batch, dpow_digests_batch_device: digests_many.cpp; dpow_search_bound) and the pure host helpers.  The three batched loops' planner and task set-up are many_plan.cpp.  The node layer is node.cpp, the dpow_diag_* entry points diag.cpp.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>

@@ -1,8 +1,9 @@
 // scan_many.cpp -- host side of the batched scan: dpow_scan_batch's launch loop over the batched
-// scan kernel (md5_scan_many.hip) on the launch engine (batch_engine.h), its planner and the host
-// helpers dpow_scan_plan and dpow_scan_plan_halve.
+// scan kernel (md5_scan_many.hip) on the launch engine (batch_engine.h) and the host helpers
+// dpow_scan_plan and dpow_scan_plan_halve.
 //
-// Launches.  The tasks are worked in array order.  A launch takes tasks from a cursor under two
+// Launches.  The tasks are worked in array order, by the planner the batched loops share
+// (many_plan.h many_next).  A launch takes tasks from a cursor under two
 // budgets: kBatchCap local indices (the cancel latency of DESIGN.md section 11) and a hit weight of
 // a quarter of the hit list (scan.cpp's slice rule, summed over the launch's parts: DESIGN.md
 // section 17).  Only its last task can be cut, at a multiple of 256 local indices from the task's
@@ -37,63 +38,21 @@
 #include "batch.h"
 #include "batch_engine.h"
 #include "ctx.h"
+#include "many_plan.h"
+#include "md5_host.h"
 #include "md5_scan_many.h"
 #include "queue.h"
 #include "scan.h"
 
 namespace dpow {
 
-uint64_t scan_many_weight(uint64_t n, uint32_t ntz) {
-    const uint32_t shift = 4u * std::min(ntz, 7u);
-    return (n + (1ull << shift) - 1ull) >> shift;
-}
-
-bool scan_many_next(const uint64_t *i_begin, const uint64_t *i_end, const uint32_t *ntz, size_t n,
-                    const ScanManyBudget &b, ScanManyCursor &cur, std::vector<ScanManyPart> &parts, uint32_t &group) {
-    parts.clear();
-    uint64_t used = 0, weight = 0;
-    while (cur.task < n) {
-        const uint64_t lo = i_begin[cur.task] + cur.done, end = i_end[cur.task];
-        if (lo >= end) {  // an empty task, or one just finished
-            cur.task++;
-            cur.done = 0;
-            continue;
-        }
-        // The most this task may add: the indices left of the first budget, and the most whose
-        // weight is left of the second (ceil(m / 16^e) <= w exactly when m <= w * 16^e).
-        const uint64_t left = end - lo;
-        const uint64_t room = std::min(b.cap - used, (b.weight - weight) << (4u * std::min(ntz[cur.task], 7u)));
-        const uint64_t take = left <= room ? left : room & ~255ull;
-        if (take == 0) break;  // (never of an empty launch: both budgets are at least 256)
-        parts.push_back(ScanManyPart{(uint32_t)cur.task, lo, lo + take});
-        used += take;
-        weight += scan_many_weight(take, ntz[cur.task]);
-        if (take < left) {
-            cur.done += take;
-            break;
-        }
-        cur.task++;
-        cur.done = 0;
-    }
-    group = batch_group(used);
-    return !parts.empty();
-}
-
-ScanManyBudget scan_many_halve(uint64_t total, uint64_t weight) {
-    const auto half = [](uint64_t x) { return std::max<uint64_t>((x / 2 + 255u) & ~255ull, 256u); };
-    return ScanManyBudget{std::min(half(total), kBatchCap), std::min<uint64_t>(half(weight), kScanCap / 4u)};
-}
-
 namespace {
 
-// DPOW_DIAG_SCAN_MANY_CAP: the candidate budget of this call's launches, rounded down to a
-// multiple of 256 (read per call: how the tests put launch seams into small windows).
-uint64_t scan_many_cap() {
-    if (const char *v = getenv("DPOW_DIAG_SCAN_MANY_CAP")) {
-        const long long c = atoll(v);
-        if (c >= 256 && (uint64_t)c <= kBatchCap) return (uint64_t)c & ~255ull;
-    }
-    return kBatchCap;
+// The budgets for planning again the parts of a launch of `total` local indices and hit weight
+// `weight` whose count overflowed its list: half of each, rounded up to a multiple of 256.
+ManyBudget scan_many_halve(uint64_t total, uint64_t weight) {
+    const auto half = [](uint64_t x) { return std::max<uint64_t>((x / 2 + 255u) & ~255ull, 256u); };
+    return ManyBudget{std::min(half(total), kBatchCap), std::min<uint64_t>(half(weight), kScanCap / 4u)};
 }
 
 // DPOW_DIAG_SCAN_MANY_LIST: the capacity of this call's hit lists (the plan stays kScanCap's).
@@ -103,18 +62,6 @@ uint32_t scan_many_capacity() {
         if (c >= (long)kScanMinCap && c <= (long)kScanCap) return (uint32_t)c;
     }
     return kScanCap;
-}
-
-// The descriptors of one launch, in task order: each part in pieces of `group` local indices.
-template <typename Emit>
-size_t scan_many_blocks(const std::vector<ScanManyPart> &parts, uint32_t group, Emit &&emit) {
-    size_t n_blocks = 0;
-    for (const ScanManyPart &p : parts) {
-        const uint32_t rows = (uint32_t)((p.hi - p.lo + group - 1) / group);
-        for (uint64_t lo = p.lo; lo < p.hi; lo += group, ++n_blocks)
-            emit(n_blocks, p.task, lo, p.hi - lo > group ? lo + group : p.hi, rows);
-    }
-    return n_blocks;
 }
 
 // The context's buffers.  Device: the task table in the engine's image area, the control words
@@ -140,8 +87,9 @@ static_assert(kManyBlocksOff % 32 == 0 && kManyOutOff % 8 == 0 && kManyOutCountO
 constexpr EngineSections kManyAt{kManyDevListOff, kManyOutOff, kManyRecOff};
 
 const char *const kWho = "dpow_scan_batch";
+const char *const kCapEnv = "DPOW_DIAG_SCAN_MANY_CAP";  // (many_plan.h many_cap)
 
-bool cursor_before(const ScanManyCursor &a, const ScanManyCursor &b) {
+bool cursor_before(const ManyCursor &a, const ManyCursor &b) {
     return a.task != b.task ? a.task < b.task : a.done < b.done;
 }
 
@@ -178,17 +126,7 @@ int scan_many_check(const dpow_scan_task *tasks, size_t n_tasks, const dpow_scan
     if (n_tasks == 0 || n_tasks > DPOW_BATCH_MAX)
         return set_error(DPOW_EINVAL, "dpow_scan_batch: n_tasks must be in [1, DPOW_BATCH_MAX]");
     if (max_hits < 256) return set_error(DPOW_EINVAL, "dpow_scan_batch: max_hits below 256 (one k's candidates)");
-    for (size_t i = 0; i < n_tasks; ++i) {
-        dpow_batch_task t{};
-        t.nonce = tasks[i].nonce;
-        t.nonce_len = tasks[i].nonce_len;
-        t.worker_byte = tasks[i].worker_byte;
-        t.k_begin = tasks[i].k_begin;
-        t.k_end = tasks[i].k_end;
-        const int rc = batch_check_task(t, kWho);
-        if (rc < 0) return rc;
-    }
-    return 0;
+    return many_check_tasks(tasks, n_tasks, kWho);
 }
 
 int scan_many_run(ScanManyState **state, hipStream_t stream, const volatile uint32_t *cancel, dpow_scan_task *tasks,
@@ -196,25 +134,16 @@ int scan_many_run(ScanManyState **state, hipStream_t stream, const volatile uint
     const size_t n = n_tasks;
     dpow_batch_stats st{};
     // A task's progress: the hits of its local indices [i_begin, i_done) are staged.
-    std::vector<uint64_t> i_begin(n), i_end(n), i_done(n), n_hits(n, 0);
-    std::vector<uint32_t> rbits(n), ntz(n);
-    bool any = false;
-    for (size_t i = 0; i < n; ++i) {
-        rbits[i] = remainder_bits(tasks[i].worker_bits);
-        ntz[i] = tasks[i].ntz;
-        i_begin[i] = i_done[i] = tasks[i].k_begin << rbits[i];
-        i_end[i] = tasks[i].k_end << rbits[i];
-        any = any || i_begin[i] < i_end[i];
-    }
+    ManyTasks v = many_tasks(tasks, n);
+    std::vector<uint64_t> n_hits(n, 0);
     std::vector<dpow_scan_hit> staged;
     // `unfinished`: the status of every task that is not done, DPOW_MORE or DPOW_CANCELLED.
     const auto write_out = [&](int unfinished, bool cancelled_on_entry) {
         uint64_t first = 0;
         for (size_t i = 0; i < n; ++i) {
             dpow_scan_task &t = tasks[i];
-            const bool finished = i_done[i] == i_end[i] && !cancelled_on_entry;  // (an empty task is)
-            t.status = finished ? DPOW_EXHAUSTED : unfinished;
-            t.k_done = finished ? t.k_end : i_done[i] >> rbits[i];
+            t.status = v.finished(i, cancelled_on_entry) ? DPOW_EXHAUSTED : unfinished;
+            t.k_done = v.k_done(i);
             t.first_hit = first;
             t.n_hits = n_hits[i];
             first += n_hits[i];
@@ -225,26 +154,16 @@ int scan_many_run(ScanManyState **state, hipStream_t stream, const volatile uint
         return 0;
     };
     if (__atomic_load_n(cancel, __ATOMIC_ACQUIRE) != 0u) return write_out(DPOW_CANCELLED, true);  // no launch
-    if (!any) return write_out(DPOW_EXHAUSTED, false);  // only empty tasks: no launch
+    if (!v.any) return write_out(DPOW_EXHAUSTED, false);  // only empty tasks: no launch
 
     int rc = scan_many_state(state, stream);
     if (rc < 0) return rc;
     EngineBuffers &s = (*state)->buf;
 
-    // The task table: row i is task i's, with its own ntz and prefilter mask; an empty task's row
-    // is never read.
-    BatchTask *const h_rows = reinterpret_cast<BatchTask *>(s.h_mem + kManyRowsOff);
-    for (size_t i = 0; i < n; ++i)
-        if (i_begin[i] < i_end[i])
-            batch_fill_task(h_rows[i], tasks[i].nonce, tasks[i].nonce_len, ntz[i], tasks[i].worker_byte,
-                            tasks[i].worker_bits);
-    BatchTask *const d_tasks = reinterpret_cast<BatchTask *>(s.d_mem);
-    {
-        const hipError_t e = batch_upload(reinterpret_cast<uint32_t *>(d_tasks),
-                                          reinterpret_cast<const uint32_t *>(s.d_h_mem + kManyRowsOff),
-                                          (uint32_t)(n * sizeof(BatchTask) / 4), stream);
-        if (e != hipSuccess) return hip_fail(e, "dpow_scan_batch: upload");
-    }
+    // The task table: row i is task i's, with its own ntz and prefilter mask.
+    if ((rc = many_upload_tasks(tasks, v, s, kManyRowsOff, stream, kWho)) < 0) return rc;
+    const BatchTask *const h_rows = reinterpret_cast<const BatchTask *>(s.h_mem + kManyRowsOff);
+    const BatchTask *const d_tasks = reinterpret_cast<const BatchTask *>(s.d_mem);
     BatchEntry *const h_blocks = reinterpret_cast<BatchEntry *>(s.h_mem + kManyBlocksOff);
     const uint32_t *const h_out = reinterpret_cast<const uint32_t *>(s.h_mem + kManyOutOff);
     const unsigned long long *const h_count =
@@ -267,11 +186,11 @@ int scan_many_run(ScanManyState **state, hipStream_t stream, const volatile uint
         return e == hipSuccess ? 0 : hip_fail(e, "dpow_scan_batch: launch");
     };
 
-    const ScanManyBudget full{scan_many_cap(), kScanCap / 4u};
-    ScanManyBudget budget = full;
-    ScanManyCursor cur, halved_until;  // the halved budgets hold while cur is before halved_until
+    const ManyBudget full{many_cap(kCapEnv), kScanCap / 4u};
+    ManyBudget budget = full;
+    ManyCursor cur, halved_until;  // the halved budgets hold while cur is before halved_until
     bool halved = false;
-    std::vector<ScanManyPart> parts;
+    std::vector<ManyPart> parts;
     std::vector<uint32_t> entries;
     std::vector<uint8_t> msg;
     uint32_t group = 0;
@@ -281,24 +200,16 @@ int scan_many_run(ScanManyState **state, hipStream_t stream, const volatile uint
             budget = full;
             halved = false;
         }
-        const ScanManyCursor start = cur;
-        if (!scan_many_next(i_begin.data(), i_end.data(), ntz.data(), n, budget, cur, parts, group)) break;
+        const ManyCursor start = cur;
+        if (!many_next(v.i_begin.data(), v.i_end.data(), v.ntz.data(), n, budget, cur, parts, group)) break;
         uint64_t total = 0, weight = 0;
-        size_t n_blocks = 0;
-        for (const ScanManyPart &p : parts) {
+        for (const ManyPart &p : parts) {
             total += p.hi - p.lo;
-            weight += scan_many_weight(p.hi - p.lo, ntz[p.task]);
-            n_blocks += (size_t)((p.hi - p.lo + group - 1) / group);
+            weight += many_weight(p.hi - p.lo, v.ntz[p.task]);
         }
-        if (n_blocks == 0 || n_blocks > kScanManyMaxBlocks)
+        const size_t n_blocks = many_write_blocks(parts, group, h_blocks, kScanManyMaxBlocks);
+        if (n_blocks == 0)
             return set_error(DPOW_EINVAL, "dpow_scan_batch: the launch plan left the descriptor table");  // never expected
-        scan_many_blocks(parts, group, [&](size_t b, uint32_t task, uint64_t lo, uint64_t hi, uint32_t) {
-            BatchEntry &e = h_blocks[b];
-            e.i_begin = lo;
-            e.i_end = hi;
-            e.task = task;
-            e.pad_[0] = e.pad_[1] = e.pad_[2] = 0;
-        });
         rc = engine_launch(s, kManyAt, (uint32_t)parts.size(), group, (uint32_t)n_blocks, stream,
                            "dpow_scan_batch: stream idle without the launch's completion record", st, issue);
         if (rc < 0) return rc;
@@ -325,12 +236,11 @@ int scan_many_run(ScanManyState **state, hipStream_t stream, const volatile uint
             return h_blocks[scan_many_entry_block(entries[q])].i_begin + scan_many_entry_off(entries[q]);
         };
         size_t j = 0, b_end = 0;  // the next entry; the descriptors of the parts so far
-        for (const ScanManyPart &p : parts) {
+        for (const ManyPart &p : parts) {
             const dpow_scan_task &t = tasks[p.task];
-            const uint32_t rb = rbits[p.task], base_tb = h_rows[p.task].base_tb;
+            const uint32_t rb = v.rbits[p.task], base_tb = h_rows[p.task].base_tb;
             b_end += (size_t)((p.hi - p.lo + group - 1) / group);
-            msg.resize(t.nonce_len + DPOW_MAX_SECRET);
-            if (t.nonce_len) memcpy(msg.data(), t.nonce, t.nonce_len);
+            md5_msg_of_nonce(msg, t.nonce, t.nonce_len);
             uint64_t prev_k = ~0ull;
             // The part's entries: the entries are sorted and the parts' descriptors follow each other.
             for (; j < entries.size() && scan_many_entry_block(entries[j]) < b_end; ++j) {
@@ -341,17 +251,17 @@ int scan_many_run(ScanManyState **state, hipStream_t stream, const volatile uint
                            (index_of(j + n_k) >> rb) == k)
                         ++n_k;
                     if (staged.size() + n_k > max_hits) {  // `out` is full: this task goes on from k
-                        i_done[p.task] = k << rb;
+                        v.i_done[p.task] = k << rb;
                         return write_out(DPOW_MORE, false);
                     }
                     prev_k = k;
                 }
                 staged.emplace_back();
-                if (!scan_fill_hit(msg.data(), t.nonce_len, global_of_local(i, rb, base_tb), ntz[p.task], staged.back()))
+                if (!scan_fill_hit(msg.data(), t.nonce_len, global_of_local(i, rb, base_tb), v.ntz[p.task], staged.back()))
                     return set_error(DPOW_EVERIFY, "dpow_scan_batch: kernel hit failed host MD5 verification");
                 n_hits[p.task]++;
             }
-            i_done[p.task] = p.hi;
+            v.i_done[p.task] = p.hi;
         }
     }
     return write_out(DPOW_EXHAUSTED, false);
@@ -372,27 +282,17 @@ extern "C" int dpow_scan_plan(const uint64_t *i_begin, const uint64_t *i_end, co
     if (capacity == 0) capacity = kScanCap;
     if (capacity < 1024 || capacity > kScanCap)
         return set_error(DPOW_EINVAL, "dpow_scan_plan: capacity outside [1024, 65536]");
-    const ScanManyBudget budget{cap & ~255ull, (uint64_t)(capacity / 4u) & ~255ull};
+    const ManyBudget budget{cap & ~255ull, (uint64_t)(capacity / 4u) & ~255ull};
     for (size_t i = 0; i < n_tasks; ++i) {
         if (i_begin[i] > i_end[i]) return set_error(DPOW_EINVAL, "dpow_scan_plan: i_begin > i_end");
         if (i_end[i] > (DPOW_K_LIMIT << 8)) return set_error(DPOW_ERANGE, "dpow_scan_plan: i_end beyond DPOW_K_LIMIT");
     }
-    ScanManyCursor cur;
-    std::vector<ScanManyPart> parts;
+    ManyCursor cur;
+    std::vector<ManyPart> parts;
     uint32_t group = 0;
     uint64_t n_out = 0, launch = 0;
-    for (; scan_many_next(i_begin, i_end, ntz, n_tasks, budget, cur, parts, group); ++launch) {
-        const size_t n_blocks =
-            scan_many_blocks(parts, group, [&](size_t b, uint32_t task, uint64_t lo, uint64_t hi, uint32_t rows) {
-                if (!out || n_out + b >= max_entries) return;
-                dpow_batch_range &o = out[n_out + b];
-                o.launch = (uint32_t)launch;
-                o.task = task;
-                o.i_begin = lo;
-                o.i_end = hi;
-                o.group = group;
-                o.rows = rows;
-            });
+    for (; many_next(i_begin, i_end, ntz, n_tasks, budget, cur, parts, group); ++launch) {
+        const size_t n_blocks = many_append_ranges(parts, group, launch, out, max_entries, n_out);
         if (n_blocks > kScanManyMaxBlocks)
             return set_error(DPOW_EINVAL, "dpow_scan_plan: a launch beyond its descriptor bound");  // never expected
         n_out += n_blocks;
@@ -403,7 +303,7 @@ extern "C" int dpow_scan_plan(const uint64_t *i_begin, const uint64_t *i_end, co
 }
 
 extern "C" void dpow_scan_plan_halve(uint64_t total, uint64_t weight, uint64_t *cap_out, uint32_t *capacity_out) {
-    const ScanManyBudget b = scan_many_halve(total, weight);
+    const ManyBudget b = scan_many_halve(total, weight);
     if (cap_out) *cap_out = b.cap;
     if (capacity_out) *capacity_out = (uint32_t)(4u * b.weight);
 }

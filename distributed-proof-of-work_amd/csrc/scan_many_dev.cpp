@@ -3,8 +3,8 @@
 // helper dpow_scan_batch_device_settle.
 //
 // Launches.  The tasks are worked in array order and the launches are the batched census's
-// (census_many_next): a launch takes tasks from a cursor until it holds kBatchCap local indices, only
-// its last task can be cut, at a multiple of 256 local indices from the task's begin, and a task's
+// (many_plan.h many_next, without a weight budget): a launch takes tasks from a cursor until it
+// holds kBatchCap local indices, only its last task can be cut, at a multiple of 256 local indices from the task's begin, and a task's
 // part is cut into workgroup descriptors of batch_group(the launch's total).  The list has no
 // capacity, hence no hit budget and no overflow path.  A launch of the plan is one mask launch,
 // whose completion record the host waits for, and behind it without a wait the rows launch (the row
@@ -40,8 +40,8 @@
 #include "../../include/dpow_worker.h"
 #include "batch.h"
 #include "batch_engine.h"
-#include "census_many.h"
 #include "ctx.h"
+#include "many_plan.h"
 #include "md5_host.h"
 #include "queue.h"
 #include "scan_dev.h"
@@ -66,16 +66,6 @@ bool scan_many_dev_settle(const BatchEntry *blocks, size_t n_fit, const uint64_t
 }
 
 namespace {
-
-// DPOW_DIAG_SCAN_MANY_DEV_CAP: the candidate budget of this call's launches, rounded down to a
-// multiple of 256 (read per call: how the tests put launch seams into small windows).
-uint64_t scan_many_dev_cap() {
-    if (const char *v = getenv("DPOW_DIAG_SCAN_MANY_DEV_CAP")) {
-        const long long c = atoll(v);
-        if (c >= 256 && (uint64_t)c <= kBatchCap) return (uint64_t)c & ~255ull;
-    }
-    return kBatchCap;
-}
 
 // The context's buffers.  Device: the task table in the engine's image area, the control words
 // behind it (batch_engine.h) with the check word at +16, then the totals, their prefix, the
@@ -113,6 +103,7 @@ static_assert(kBlocksOff % 32 == 0 && kBlocksBytes % 32 == 0 && kTableOff % 8 ==
 constexpr EngineSections kAt{kTotalsOff, kOutPrefixOff, kRecOff};
 
 const char *const kWho = "dpow_scan_batch_device";
+const char *const kCapEnv = "DPOW_DIAG_SCAN_MANY_DEV_CAP";  // (many_plan.h many_cap)
 
 }  // namespace
 
@@ -166,17 +157,7 @@ int scan_many_dev_check(const dpow_scan_task *tasks, size_t n_tasks, const void 
         return set_error(DPOW_EINVAL, "dpow_scan_batch_device: n_tasks must be in [1, DPOW_BATCH_MAX]");
     if (max_hits < DPOW_SCAN_DEVICE_MIN_HITS)
         return set_error(DPOW_EINVAL, "dpow_scan_batch_device: max_hits below 16384 (one workgroup's candidates)");
-    for (size_t i = 0; i < n_tasks; ++i) {
-        dpow_batch_task t{};
-        t.nonce = tasks[i].nonce;
-        t.nonce_len = tasks[i].nonce_len;
-        t.worker_byte = tasks[i].worker_byte;
-        t.k_begin = tasks[i].k_begin;
-        t.k_end = tasks[i].k_end;
-        const int rc = batch_check_task(t, kWho);
-        if (rc < 0) return rc;
-    }
-    return 0;
+    return many_check_tasks(tasks, n_tasks, kWho);
 }
 
 int scan_many_dev_run(ScanManyDevState **state, hipStream_t stream, const volatile uint32_t *cancel,
@@ -185,23 +166,14 @@ int scan_many_dev_run(ScanManyDevState **state, hipStream_t stream, const volati
     const size_t n = n_tasks;
     dpow_batch_stats st{};
     // A task's progress: the hits of its local indices [i_begin, i_done) are in the list.
-    std::vector<uint64_t> i_begin(n), i_end(n), i_done(n);
-    std::vector<uint32_t> rbits(n);
-    bool any = false;
-    for (size_t i = 0; i < n; ++i) {
-        rbits[i] = remainder_bits(tasks[i].worker_bits);
-        i_begin[i] = i_done[i] = tasks[i].k_begin << rbits[i];
-        i_end[i] = tasks[i].k_end << rbits[i];
-        any = any || i_begin[i] < i_end[i];
-    }
+    ManyTasks v = many_tasks(tasks, n);
     // `rows`: the n + 1 row pointers (null: all zero).  `unfinished`: the status of every task that
     // is not done, DPOW_MORE or DPOW_CANCELLED.
     const auto write_out = [&](const uint64_t *rows, int unfinished, bool cancelled_on_entry) {
         for (size_t i = 0; i < n; ++i) {
             dpow_scan_task &t = tasks[i];
-            const bool finished = i_done[i] == i_end[i] && !cancelled_on_entry;  // (an empty task is)
-            t.status = finished ? DPOW_EXHAUSTED : unfinished;
-            t.k_done = finished ? t.k_end : i_done[i] >> rbits[i];
+            t.status = v.finished(i, cancelled_on_entry) ? DPOW_EXHAUSTED : unfinished;
+            t.k_done = v.k_done(i);
             t.first_hit = rows ? rows[i] : 0;
             t.n_hits = rows ? rows[i + 1] - rows[i] : 0;
         }
@@ -219,27 +191,17 @@ int scan_many_dev_run(ScanManyDevState **state, hipStream_t stream, const volati
         return write_out(nullptr, unfinished, cancelled_on_entry);
     };
     if (__atomic_load_n(cancel, __ATOMIC_ACQUIRE) != 0u) return no_launch(DPOW_CANCELLED, true);
-    if (!any) return no_launch(DPOW_EXHAUSTED, false);  // only empty tasks: no launch, nothing allocated
+    if (!v.any) return no_launch(DPOW_EXHAUSTED, false);  // only empty tasks: no launch, nothing allocated
 
     int rc = scan_many_dev_state(state, stream);
     if (rc < 0) return rc;
     ScanManyDevState &sd = **state;
     EngineBuffers &s = sd.buf;
 
-    // The task table: row i is task i's, with its own ntz and prefilter mask; an empty task's row
-    // is never read.
-    BatchTask *const h_rows = reinterpret_cast<BatchTask *>(s.h_mem + kTaskRowsOff);
-    for (size_t i = 0; i < n; ++i)
-        if (i_begin[i] < i_end[i])
-            batch_fill_task(h_rows[i], tasks[i].nonce, tasks[i].nonce_len, tasks[i].ntz, tasks[i].worker_byte,
-                            tasks[i].worker_bits);
-    BatchTask *const d_tasks = reinterpret_cast<BatchTask *>(s.d_mem);
-    {
-        const hipError_t e = batch_upload(reinterpret_cast<uint32_t *>(d_tasks),
-                                          reinterpret_cast<const uint32_t *>(s.d_h_mem + kTaskRowsOff),
-                                          (uint32_t)(n * sizeof(BatchTask) / 4), stream);
-        if (e != hipSuccess) return hip_fail(e, "dpow_scan_batch_device: upload");
-    }
+    // The task table: row i is task i's, with its own ntz and prefilter mask.
+    if ((rc = many_upload_tasks(tasks, v, s, kTaskRowsOff, stream, kWho)) < 0) return rc;
+    const BatchTask *const h_rows = reinterpret_cast<const BatchTask *>(s.h_mem + kTaskRowsOff);
+    const BatchTask *const d_tasks = reinterpret_cast<const BatchTask *>(s.d_mem);
     unsigned long long *const out = static_cast<unsigned long long *>(d_idx_out);
     uint8_t *const tz_out = static_cast<uint8_t *>(d_tz_out);
     unsigned long long *const rows_dev =
@@ -271,9 +233,9 @@ int scan_many_dev_run(ScanManyDevState **state, hipStream_t stream, const volati
         else (void)hipGetLastError();
     };
 
-    const uint64_t cap = scan_many_dev_cap();
-    CensusManyCursor cur;
-    std::vector<CensusManyPart> parts;
+    const ManyBudget budget{many_cap(kCapEnv), 0};
+    ManyCursor cur;
+    std::vector<ManyPart> parts;
     uint32_t group = 0, next_row = 0;
     size_t placed_total = 0;
     int unfinished = DPOW_EXHAUSTED;  // (nothing is unfinished when the plan runs out)
@@ -282,27 +244,15 @@ int scan_many_dev_run(ScanManyDevState **state, hipStream_t stream, const volati
             unfinished = DPOW_CANCELLED;
             break;
         }
-        if (!census_many_next(i_begin.data(), i_end.data(), n, cap, cur, parts, group)) break;
+        if (!many_next(v.i_begin.data(), v.i_end.data(), nullptr, n, budget, cur, parts, group)) break;
         BatchEntry *const h_blocks = reinterpret_cast<BatchEntry *>(s.h_mem + kBlocksOff + half * kBlocksBytes);
         const BatchEntry *const p_blocks =
             reinterpret_cast<const BatchEntry *>(s.d_h_mem + kBlocksOff + half * kBlocksBytes);  // pinned
         uint64_t candidates = 0;
-        size_t n_blocks = 0;
-        for (const CensusManyPart &p : parts) {
-            candidates += p.hi - p.lo;
-            n_blocks += (size_t)((p.hi - p.lo + group - 1) / group);
-        }
-        if (n_blocks == 0 || n_blocks > kScanManyMaxBlocks || group > kBatchMaxGroup)
+        for (const ManyPart &p : parts) candidates += p.hi - p.lo;
+        const size_t n_blocks = many_write_blocks(parts, group, h_blocks, kScanManyMaxBlocks);
+        if (n_blocks == 0 || group > kBatchMaxGroup)
             return fail(set_error(DPOW_EINVAL, "dpow_scan_batch_device: the launch plan left the descriptor table"));  // never expected
-        size_t b = 0;
-        for (const CensusManyPart &p : parts)
-            for (uint64_t lo = p.lo; lo < p.hi; lo += group, ++b) {
-                BatchEntry &e = h_blocks[b];
-                e.i_begin = lo;
-                e.i_end = p.hi - lo > group ? lo + group : p.hi;
-                e.task = p.task;
-                e.pad_[0] = e.pad_[1] = e.pad_[2] = 0;
-            }
         // A short descriptor table is read where it is, in pinned memory, one scalar load per
         // workgroup; a long one is first copied to device memory by the upload kernel.
         const bool copy = n_blocks >= kQueueCopyBlocks;
@@ -338,7 +288,7 @@ int scan_many_dev_run(ScanManyDevState **state, hipStream_t stream, const volati
         if (placed > room)
             return fail(set_error(DPOW_EVERIFY, "dpow_scan_batch_device: a prefix that does not ascend"));
         uint32_t n_entries = 0;
-        if (!scan_many_dev_settle(h_blocks, n_fit, i_begin.data(), i_done.data(), n, next_row, h_table, n_entries))
+        if (!scan_many_dev_settle(h_blocks, n_fit, v.i_begin.data(), v.i_done.data(), n, next_row, h_table, n_entries))
             return fail(set_error(DPOW_EINVAL, "dpow_scan_batch_device: a descriptor out of its task's order"));  // never expected
         // (A launch without a hit whose tasks began earlier queues nothing behind its mask launch.)
         const bool queued = n_entries != 0u || placed != 0u;
@@ -427,11 +377,10 @@ int scan_many_dev_run(ScanManyDevState **state, hipStream_t stream, const volati
                 const dpow_scan_task &t = tasks[task];
                 const uint64_t g = smp[q].idx;
                 uint64_t i;
-                ok = local_of_global(g, rbits[task], h_rows[task].base_tb, i) && i >= i_begin[task] && i < i_done[task];
+                ok = local_of_global(g, v.rbits[task], h_rows[task].base_tb, i) && i >= v.i_begin[task] &&
+                     i < v.i_done[task];
                 if (ok) {
-                    msg.resize(t.nonce_len + DPOW_MAX_SECRET);
-                    if (t.nonce_len) memcpy(msg.data(), t.nonce, t.nonce_len);
-                    const uint32_t tz = md5_depth_of_index(msg.data(), t.nonce_len, g);
+                    const uint32_t tz = md5_depth_of_index(md5_msg_of_nonce(msg, t.nonce, t.nonce_len), t.nonce_len, g);
                     ok = tz >= t.ntz && (!tz_out || smp[q].tz == tz);
                 }
             }

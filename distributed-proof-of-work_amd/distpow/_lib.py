@@ -17,7 +17,7 @@ import sys
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 INCLUDE = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include")
-# DPOW_LIB_PATH overrides the in-tree library (A/B builds in tools/ab_variants.py only;
+# DPOW_LIB_PATH overrides the in-tree library (A/B builds in tools/ab_variants.py and tools/many_host_ab.py only;
 # such a library is not checked against the source hash, but its ABI version must be
 # this binding's: check_abi).
 LIB_OVERRIDE = os.environ.get("DPOW_LIB_PATH")

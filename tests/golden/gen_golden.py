@@ -86,7 +86,14 @@ Every case is also checked against SURVEY.md Appendix A where the survey lists i
     non-zero segment addition); the layouts of the cases and "unreachable"
     are all 72.  The same hints give the same file, byte for byte.
 
-Usage:  python tests/golden/gen_golden.py [--big] | --deep | --seg-inner | --layouts
+  * --many-plans: tests/golden/many_plans.json, the launch plans of the batched census and the
+    batched scan (dpow_census_plan, dpow_scan_plan) and dpow_scan_plan_halve's budgets for a fixed
+    list of cases, as the library in the tree returns them: per plan the launch count, the entry
+    count and the SHA-256 of the dpow_batch_range rows (tests/_many_plan_cases.py expands a case's
+    tasks).  CPU only.  It pins the plans of one commit for the commits after it, so it is run
+    before a change to the planner, never after (tests/test_many_plans_golden.py compares).
+
+Usage:  python tests/golden/gen_golden.py [--big] | --deep | --seg-inner | --layouts | --many-plans
 """
 import argparse
 import ctypes
@@ -617,8 +624,99 @@ def layouts(path):
           f"tz >= 9 entry in the second segment, {time.time() - t_all:.0f} s", file=sys.stderr)
 
 
+def _gpu_test_seam_tasks():
+    """The task sets whose launch seams tests/test_gpu_scan_many.py (_seam_tasks: the same draws from
+    random.Random(5), without the nonces) and tests/test_gpu_census_many.py (test_launch_seams) walk."""
+    rnd = random.Random(5)
+    scan = [(253, 259, 0, 1), (65536 - 1536, 65536 + 1536, 8, 0), (65533, 65539, 0, 2), (254, 258, 0, 0)]
+    while len(scan) < 30:
+        wbits = rnd.choice((0, 0, 1, 3, 8))
+        k0 = rnd.choice((0, 250, 65530))
+        rnd.randrange(0, 130)  # (the nonce's length)
+        ntz = rnd.choice((0, 1, 2, 3))
+        rnd.randrange(1 << wbits)  # (the worker byte)
+        scan.append((k0, k0 + rnd.randrange(1, 14), wbits, ntz))
+    census = [[(k0 + 0, k0 + n, 3, 0) for n in sizes]
+              for sizes, k0 in (((1000, 5000, 256, 12288, 3), 0), ((100, 3, 2, 200, 1, 130), 65500))]
+    return scan, census
+
+
+def many_plans_cases():
+    """(name, tasks spec, [(plan, cap, capacity), ...]) of many_plans.json; _many_plan_cases.expand reads a spec."""
+    every_cap, every_capacity = (256, 4096, 1 << 28), (1024, 65536)
+    both = [("census", c, 0) for c in (0,) + every_cap] + [("scan", c, y) for c in (0,) + every_cap for y in every_capacity]
+    big = [p for p in both if p[1] in (0, 1 << 28)]  # (a small budget would make millions of entries of a long task)
+    scan_seams, census_seams = _gpu_test_seam_tasks()
+    mixed = {"seed": 11, "n": 96, "worker_bits": [0, 3, 8], "ntz": [0, 1, 6, 7, 9], "k_starts": [0, 250, 65530, 1 << 24],
+             "max_k": 300, "empty": 7}
+    cases = [
+        ("one task", {"list": [[3, 1003, 0, 3]]}, both),
+        ("one task of three launches", {"list": [[5, 5 + (3 << 20), 0, 9]]}, big),
+        ("4096 tasks of 256 indices", {"repeat": [7, 8, 0, 1], "n": 4096}, both),
+        ("4096 tasks of one index", {"repeat": [70000, 70001, 8, 0], "n": 4096}, both),
+        ("empty tasks at the front, in the middle and at the end",
+         {"list": [[9, 9, 0, 1], [0, 0, 3, 0], [4, 30, 0, 1], [77, 77, 8, 6], [1 << 30, 1 << 30, 0, 9], [250, 270, 3, 0],
+                   [12, 12, 0, 7], [5, 5, 8, 0]]}, both),
+        ("only empty tasks", {"list": [[9, 9, 0, 1], [0, 0, 3, 0], [1 << 40, 1 << 40, 8, 9]]}, both),
+        # 2560, 6656 and 1280 indices under 4096: the second is cut after 1536 and after 5632
+        ("a task cut by two seams", {"list": [[0, 10, 0, 2], [10, 36, 0, 2], [0, 5, 0, 2]]},
+         [("census", 4096, 0), ("scan", 4096, 65536), ("scan", 4096, 1024)]),
+        ("mixed widths and depths", mixed, both),
+        ("many mixed tasks", dict(mixed, seed=12, n=4096, max_k=40), both),
+        ("long and short tasks, deep and shallow",
+         {"list": [[0, 1 << 21, 0, 7], [5, 9, 3, 0], [100, 100 + (1 << 20), 0, 9], [0, 300, 8, 1],
+                   [1 << 24, (1 << 24) + (3 << 19), 3, 6], [0, 40, 0, 0], [65530, 65530 + (1 << 12), 0, 1],
+                   [1 << 32, (1 << 32) + (1 << 28), 8, 7], [255, 257, 0, 9]]}, big),
+        ("test_gpu_scan_many seams", {"list": [list(t) for t in scan_seams]},
+         [("scan", c, 0) for c in (0, 512, 768)] + [("census", c, 0) for c in (0, 512, 768)]),
+    ]
+    for j, tasks in enumerate(census_seams):
+        cases.append((f"test_gpu_census_many seams {j}", {"list": [list(t) for t in tasks]},
+                      [("census", 4096, 0), ("census", 0, 0), ("scan", 4096, 0)]))
+    return cases
+
+
+MANY_PLANS_HALVE = [(256, 256), (1 << 28, 16384), (257, 1), (512, 512), (513, 300), (1000, 16384), (65536, 4096),
+                    (1 << 20, 1 << 16), ((1 << 28) - 256, 16383), (1 << 27, 255), (3 << 26, 9999), (1 << 29, 1 << 20)]
+
+
+def many_plans(path):
+    """tests/golden/many_plans.json: what dpow_census_plan, dpow_scan_plan and dpow_scan_plan_halve of
+    the library in the tree return for a fixed list of cases -- per plan the launch count, the entry
+    count and the SHA-256 of the returned dpow_batch_range rows.  Recorded before the three batched
+    host loops were put on one planner, to pin the plans across that change: it is not run again
+    when the planner changes, the committed file is the yardstick."""
+    for p in (os.path.join(ROOT, "distributed-proof-of-work_amd"), os.path.join(ROOT, "tests")):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+    import distpow
+    from _many_plan_cases import census_windows, digest, expand, scan_windows
+    out = {"build_id": distpow.build_id(), "cases": [], "halve": []}
+    for name, spec, plans in many_plans_cases():
+        tasks = expand(spec)
+        rows = []
+        for plan, cap, capacity in plans:
+            if plan == "census":
+                blocks, launches = distpow.census_plan(census_windows(tasks), cap)
+            else:
+                blocks, launches = distpow.scan_plan(scan_windows(tasks), cap, capacity)
+            rows.append({"plan": plan, "cap": cap, "capacity": capacity, "launches": launches, "entries": len(blocks),
+                         "sha256": digest(blocks)})
+            print(f"{name}: {plan} cap {cap} capacity {capacity}: {launches} launches, {len(blocks)} entries",
+                  file=sys.stderr)
+        out["cases"].append({"name": name, "tasks": spec, "n_tasks": len(tasks), "plans": rows})
+    for total, weight in MANY_PLANS_HALVE:
+        cap, capacity = distpow.scan_plan_halve(total, weight)
+        out["halve"].append({"total": total, "weight": weight, "cap": cap, "capacity": capacity})
+    with open(path, "w") as f:
+        json.dump(out, f, separators=(",", ":"))
+        f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--many-plans", action="store_true",
+                    help="write many_plans.json: digests of the batched census's and the batched scan's launch plans")
     ap.add_argument("--layouts", action="store_true",
                     help="write layout_deep_hits.json from layout_hints.json: all-hits lists per layout (fast_scan)")
     ap.add_argument("--big", action="store_true", help="also compute N=7/8 cases via the C oracle")
@@ -626,6 +724,9 @@ def main():
     ap.add_argument("--seg-inner", action="store_true",
                     help="write seg_inner_hits.json: all-hits lists for the segment-inner kernels (fast_scan)")
     args = ap.parse_args()
+    if args.many_plans:
+        many_plans(os.path.join(HERE, "many_plans.json"))
+        return
     if args.layouts:
         layouts(os.path.join(HERE, "layout_deep_hits.json"))
         return

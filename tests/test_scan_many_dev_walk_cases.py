@@ -8,7 +8,7 @@ That walk also runs the sets of tests/test_gpu_listing_walk.py (families A, B, F
 tests/test_listing_walk_cases.py's test_every_window_is_one_descriptor_from_its_begin already shows them
 under census_plan -- every task of a set is one descriptor from its window's begin, family F's whole
 descriptors from it -- and census_plan is this unit's planner (csrc/scan_many_dev.cpp runs
-census_many_next), so nothing of that is repeated here; its vacuity conditions for those sets are
+many_next), so nothing of that is repeated here; its vacuity conditions for those sets are
 test_the_device_scan_tests_cannot_pass_vacuously's."""
 import collections
 import hashlib
